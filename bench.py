@@ -17,7 +17,10 @@ with one bitmap all-to-all over RCCL/xGMI (the owner-side OR is GoExecutor's per
 value = edges scanned by all queries (whole-query counts, summed over ranks in the library) / max
 time over ranks.  torch.distributed (gloo) only carries the RCCL unique id, barriers and timings.
 
-Also reported, outside the timed region: the dominant kernel's algorithmic HBM bandwidth (HIP
+A plain run loads the graph, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs DIR is given (dump_outputs) and prints the result line.
+
+With --full also reported, outside the timed region: the dominant kernel's algorithmic HBM bandwidth (HIP
 events inside the library) against the 8 TB/s peak, the end-to-end algorithmic fraction, the
 host-delivered result rate (nbg_go: rows copied to the host), a device-digest check of the
 headline queries against the CPU CSR oracle, FIND SHORTEST PATH latency (C4), the C2 RMAT-22 leg,
@@ -136,15 +139,113 @@ def run_queries(stmt, roots, inflight):
     return scanned, rows
 
 
-def go_leg(eng, stmt, roots, args, barrier, inflight, profile=True):
-    """Warm-up, the timed K steps, per-query latency, then the instrumented roofline passes."""
+def run_queries_kept(stmt, roots, inflight, keep):
+    """run_queries for the step whose outputs --dump-outputs writes: the same calls in the same
+    order, and every query's (rows, edges scanned) goes to keep["stats"] in root order.  The
+    results of the queries still in flight once the last root is submitted (of the last query
+    when one runs at a time) are not freed: they go to keep["tail"] as (query index, result), so
+    no query slot of this step has to run on while its previous result is still held."""
+    scanned = rows = 0
+    pending, stats, tail = [], keep["stats"], keep["tail"]
+    for q, r in enumerate(roots):
+        if inflight and len(pending) == inflight:
+            res = stmt.wait(pending.pop(0))
+            e, n = res.edges_scanned, res.count
+            scanned += e
+            rows += n
+            stats.append((n, e))
+            res.free()
+        if inflight:
+            pending.append(stmt.submit([r]))
+        else:
+            res = stmt.run_device([r])
+            e, n = res.edges_scanned, res.count
+            scanned += e
+            rows += n
+            stats.append((n, e))
+            if q == len(roots) - 1:
+                tail.append((q, res))
+            else:
+                res.free()
+    first = len(roots) - len(pending)
+    for i, tk in enumerate(pending):
+        res = stmt.wait(tk)
+        e, n = res.edges_scanned, res.count
+        scanned += e
+        rows += n
+        stats.append((n, e))
+        tail.append((first + i, res))
+    return scanned, rows
+
+
+DUMP_SAMPLE_BYTES = 48 << 20   # the row sample's share of the 64 MB a dump may take
+DUMP_SAMPLE_MUL = 0x9E3779B97F4A7C15   # row r is sampled when the top 8 bits of cell_0 * this are 0
+
+
+def _halves(a):
+    """int64 / uint64 payloads as exact float64 pairs: (high 32 bits, low 32 bits)."""
+    u = np.ascontiguousarray(a).view(np.uint64)
+    return (u >> np.uint64(32)).astype(np.float64), (u & np.uint64(0xFFFFFFFF)).astype(np.float64)
+
+
+def dump_outputs(path, keep, rank, world):
+    """--dump-outputs: what the last timed step's queries returned, as float64 .npy files (64-bit
+    payloads as (high, low) 32-bit halves, exact in float64).  Device rows come in no fixed order,
+    so the row sample is a fixed subset of the row values, sorted:
+      go_rows / go_edges_scanned [Q]: every query's row count and edges scanned, in root order;
+      go_tail_digest [T, 6]: for the step's last T queries (those kept by run_queries_kept): query
+        index, rows, and nbg_rows_digest's xor and sum as halves;
+      go_tail_rows_sample [M, 1 + 2 C]: of the same queries' rows, those whose first cell c has
+        (c * DUMP_SAMPLE_MUL mod 2^64) >> 56 == 0 (1 in 256), sorted per query and cut to an equal
+        share of DUMP_SAMPLE_BYTES: query index, then every cell as halves.
+    On a partitioned engine every rank writes its own rows (<name>.rank<r>.npy)."""
+    os.makedirs(path, exist_ok=True)
+    sfx = "" if world == 1 else f".rank{rank}"
+
+    def save(name, a):
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), np.asarray(a, np.float64))
+
+    stats = np.array(keep["stats"], np.float64).reshape(-1, 2)
+    save("go_rows", stats[:, 0])
+    save("go_edges_scanned", stats[:, 1])
+    digests, samples = [], []
+    for q, res in keep["tail"]:
+        n, x, s = res.digest()
+        xs = _halves(np.array([x, s], np.uint64))
+        digests.append([q, n, xs[0][0], xs[1][0], xs[0][1], xs[1][1]])
+        cols = res.fetch_bits(copy=False)   # views of the pinned host copy (valid until free)
+        if cols and len(cols[0]):
+            width = 1 + 2 * len(cols)
+            cap = DUMP_SAMPLE_BYTES // (8 * width * len(keep["tail"]))
+            pick = np.flatnonzero((cols[0].view(np.uint64) * np.uint64(DUMP_SAMPLE_MUL)) >> np.uint64(56) == 0)
+            sel = [c[pick] for c in cols]
+            order = np.lexsort(sel[::-1])[:cap]
+            block = [np.full(len(order), float(q))]
+            for c in sel:
+                block += _halves(c[order])
+            samples.append(np.stack(block, axis=1))
+        res.free()
+    keep["tail"].clear()
+    save("go_tail_digest", np.array(digests, np.float64).reshape(-1, 6))
+    save("go_tail_rows_sample", np.concatenate(samples) if samples else np.zeros((0, 3)))
+    log(f"outputs of the last timed step written to {path}")
+
+
+def go_leg(eng, stmt, roots, args, barrier, inflight, profile=True, dump=None):
+    """Warm-up and the timed K steps (dump = (rank, world): the last step's outputs are then
+    written to --dump-outputs); with --full also per-query latency and the instrumented roofline
+    passes."""
     for _ in range(args.warmup):
         run_queries(stmt, roots, inflight)
+    keep = {"stats": [], "tail": []} if dump and args.dump_outputs else None
     barrier()
     t0 = time.perf_counter()
     scanned = rows = 0
     for k in range(args.steps):
-        s, r = run_queries(stmt, roots, inflight)
+        if keep is not None and k == args.steps - 1:
+            s, r = run_queries_kept(stmt, roots, inflight, keep)
+        else:
+            s, r = run_queries(stmt, roots, inflight)
         scanned += s
         rows += r
         if time.perf_counter() - t0 > 60 and k + 1 < args.steps:   # (a long run says it is alive)
@@ -152,6 +253,10 @@ def go_leg(eng, stmt, roots, args, barrier, inflight, profile=True):
     barrier()
     elapsed = time.perf_counter() - t0
     log(f"GO timed steps done: {elapsed:.2f}s")
+    if keep is not None:
+        dump_outputs(args.dump_outputs, keep, *dump)
+    if not args.full:
+        return {"scanned": scanned, "rows": rows, "elapsed": elapsed}
     lats = []
     for _ in range(4):   # per-query latency: one query at a time, 4 passes over the roots
         for r in roots:
@@ -485,7 +590,8 @@ def verify_shortest(csr, pairs, sp_paths, upto):
     return out
 
 
-def load_engine(scale, args, world, rank, local, comm_init):
+def load_engine(scale, args, world, rank, local, comm_init, after_gen=None):
+    """Generate, stage and finalize RMAT-scale; after_gen() is called once the samples exist."""
     from nebula_amd import Engine, rmat
     t0 = time.time()
     if world > 1 and rank != 0:
@@ -496,6 +602,8 @@ def load_engine(scale, args, world, rank, local, comm_init):
     else:
         src, dst, w = rmat.rmat_edges_fast(scale)
     gen_s = time.time() - t0
+    if after_gen is not None:
+        after_gen()
     eng = Engine(args.parts, num_gpus=world, rank=rank, device=local)
     if world > 1:
         comm_init(eng)
@@ -528,6 +636,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline's timed steps: query latency, roofline passes, "
+                         "host-delivered rate, verification against the CSR oracle, FIND SHORTEST PATH, the "
+                         "C1 / C2 / C5 / getBound legs, partition figures and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--scale", type=int, default=None, help="RMAT scale (default 26; --weak: 22 + log2 N)")
     ap.add_argument("--weak", action="store_true", help="weak scaling: RMAT-(22 + log2 N), 64 roots")
     ap.add_argument("--roots", type=int, default=None, help="queries per step (default 16 at RMAT-26, else 64)")
@@ -593,29 +707,40 @@ def main():
     model, threads, ncpu = cpu_info()
 
     # ---------------- headline: GO 3 STEPS on RMAT-scale (C3 at N GPUs), FIND SHORTEST PATH (C4)
-    src, dst, w, eng, gen_s, load_s, ready = load_engine(args.scale, args, world, rank, local, comm_init)
+    # a plain run works out the vertex sets (the roots are drawn from them) on a host thread beside
+    # the load, whose staging and device build leave most host cores idle; --full keeps the two in
+    # sequence, so its load_seconds stay comparable with the recorded runs
+    import threading
+    verts = []
+    side = threading.Thread(target=lambda: verts.append(rmat.vertex_sets(args.scale)))
+    src, dst, w, eng, gen_s, load_s, ready = load_engine(args.scale, args, world, rank, local, comm_init,
+                                                         after_gen=None if args.full else side.start)
     st = eng.stats()
-    src_verts, all_verts = rmat.vertex_sets(args.scale)
+    if args.full:
+        verts.append(rmat.vertex_sets(args.scale))
+    else:
+        side.join()
+    src_verts, all_verts = verts.pop()
     roots = [int(x) for x in rmat.pick_roots(src, args.roots, 42, verts=src_verts)]
-    pairs = rmat.pick_pairs(src, dst, args.sp_pairs, 7, verts=all_verts) if args.sp_pairs > 0 else []
+    pairs = rmat.pick_pairs(src, dst, args.sp_pairs, 7, verts=all_verts) if args.full and args.sp_pairs > 0 else []
     del src_verts, all_verts
-    if rank != 0:   # only rank 0 keeps the samples (CSR oracle / CPU baselines)
+    if rank != 0 or not args.full:   # only --full's rank 0 keeps the samples (CSR oracle / CPU baselines)
         del src, dst, w
         src = dst = w = None
     stmt = eng.prepare_go([1], args.go_steps, where)
-    g = go_leg(eng, stmt, roots, args, barrier, inflight)
+    g = go_leg(eng, stmt, roots, args, barrier, inflight, dump=(rank, world))
     workload = (f"RMAT-{args.scale}", len(roots)) if world == 1 and args.go_steps == 3 else None
     roofline, kernels = roofline_of(g, workload, args.steps)
-    delivered = host_delivered(stmt, roots[:8]) if world == 1 else None
+    delivered = host_delivered(stmt, roots[:8]) if args.full and world == 1 else None
     # device digests of the first headline queries (summed over ranks: rows stay where produced)
     dig = []
-    for r in roots[:args.verify]:
+    for r in roots[:args.verify] if args.full else []:
         res = stmt.run_device([r])
         dig.append(list(res.digest()) + [res.edges_scanned])
         res.free()
     stmt.free()
     log("GO leg done")
-    fixed = partitioned_costs(eng, roots[:4], barrier) if world > 1 else None
+    fixed = partitioned_costs(eng, roots[:4], barrier) if args.full and world > 1 else None
     if fixed is not None:
         log("partitioned fixed-cost leg done")
     sp = None
@@ -710,7 +835,7 @@ def main():
     verify = None
     cpu_csr = None
     part_load = None
-    if (args.verify or not args.no_cpu_baseline) and world >= 1:
+    if args.full and (args.verify or not args.no_cpu_baseline):
         try:
             from tests.support.oracle import CsrOracle, Y_DST
             t0 = time.time()
@@ -743,19 +868,20 @@ def main():
             log(f"verification / CSR baseline unavailable: {ex}")
     del src, dst, w
 
-    # ---------------- secondary legs (one GPU)
+    # ---------------- secondary legs (one GPU, --full)
+    single = args.full and world == 1
     c2 = None
-    if world == 1 and args.c2 and args.scale != 22:
+    if single and args.c2 and args.scale != 22:
         c2 = c2_leg(args, barrier, inflight)
-    c5 = c5_leg(args, barrier, threads, model, ncpu) if world == 1 and args.c5_scale > 0 else None
-    getbound = getbound_leg(args) if world == 1 and args.getbound_reqs > 0 else None
-    c1 = c1_leg(args) if world == 1 and args.c1_reqs > 0 else None
+    c5 = c5_leg(args, barrier, threads, model, ncpu) if single and args.c5_scale > 0 else None
+    getbound = getbound_leg(args) if single and args.getbound_reqs > 0 else None
+    c1 = c1_leg(args) if single and args.c1_reqs > 0 else None
 
     # cpu_baseline: the CSR OpenMP oracle on the headline graph and query (a bounded sample of the
     # same workload); the storaged-faithful restatement (RowSet encode/decode per hop), whose
     # key/value store does not fit RMAT-26 in a bounded sample, is attached beside it on RMAT-22
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if single and not args.no_cpu_baseline:
         faithful = faithful_baseline(args, where, threads, model, ncpu)
         if faithful is not None:
             full = committed_faithful()
@@ -769,7 +895,7 @@ def main():
     if sp is not None and cpu_csr is not None:
         sp["cpu_baseline"] = cpu_csr.get("shortest")
 
-    lat_ms = np.array(g["lat"]) * 1e3
+    lat_ms = np.array(g["lat"]) * 1e3 if args.full else None
     out = {
         "metric": METRIC,
         "value": tot_scanned / max_elapsed,
@@ -794,11 +920,11 @@ def main():
         "roofline": roofline,
         "cpu_baseline": cpu,
         "verification": verify,
-        "query_latency_ms": {"p50": float(np.percentile(lat_ms, 50)), "p90": float(np.percentile(lat_ms, 90)),
-                             "p99": float(np.percentile(lat_ms, 99)), "max": float(lat_ms.max()),
-                             "queries": len(lat_ms),
-                             "timing": "one query at a time (nbg_go_execute, rows left in HBM), 4 passes over the "
-                                       "roots; the statement's row buffers were sized by nbg_go_prepare"},
+        "query_latency_ms": None if lat_ms is None else {
+            "p50": float(np.percentile(lat_ms, 50)), "p90": float(np.percentile(lat_ms, 90)),
+            "p99": float(np.percentile(lat_ms, 99)), "max": float(lat_ms.max()), "queries": len(lat_ms),
+            "timing": "one query at a time (nbg_go_execute, rows left in HBM), 4 passes over the "
+                      "roots; the statement's row buffers were sized by nbg_go_prepare"},
         "rows_per_step": int(tot_rows) // max(1, args.steps),
         "edges_per_step": int(tot_scanned) // max(1, args.steps),
         "host_delivered": delivered,
@@ -814,6 +940,11 @@ def main():
         "load_seconds": round(load_s, 2),
         "ranks": ranks_res,
     }
+    if not args.full:   # a plain run reports its timed steps; what --full measures is left out of the line
+        for k in ("roofline", "cpu_baseline", "verification", "query_latency_ms", "host_delivered", "kernels",
+                  "find_shortest_path", "c2_rmat22", "c5_substitute", "getbound", "c1_nba", "partition_load",
+                  "partitioned_fixed_costs"):
+            del out[k]
     # the metric's second half (FIND SHORTEST PATH p50) as top-level keys at the END of the line,
     # so a reader that keeps only the line's tail (or its top-level keys) still sees it
     if sp:

@@ -8,7 +8,7 @@ OUT=gpurun_out/$1
 mkdir -p "$OUT"
 ( while sleep 30; do echo "heartbeat $(date +%T) $(tail -c 200 "$OUT/bench26.log" 2>/dev/null | tail -1)"; done ) &
 HB=$!
-timeout -k 10 1000 python -u bench.py --scale 26 --roots 16 --sp-pairs 10000 --no-cpu-baseline --c5-scale 0 \
+timeout -k 10 1000 python -u bench.py --full --scale 26 --roots 16 --sp-pairs 10000 --no-cpu-baseline --c5-scale 0 \
   > "$OUT/bench26.json" 2> "$OUT/bench26.log"
 rc=$?
 kill $HB

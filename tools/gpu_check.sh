@@ -15,10 +15,10 @@ for step in "$@"; do
       timeout -k 10 600 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread \
         > "$OUT/pytest_gpu.log" 2>&1 || { tail -30 "$OUT/pytest_gpu.log"; exit 1; } ;;
     bench)
-      timeout -k 10 600 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.log" || { tail -30 "$OUT/bench.log"; exit 1; } ;;
+      timeout -k 10 600 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.log" || { tail -30 "$OUT/bench.log"; exit 1; } ;;
     prof)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-        python3 -u bench.py --sp-pairs 2000 --no-cpu-baseline --sync > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.log" \
+        python3 -u bench.py --full --sp-pairs 2000 --no-cpu-baseline --sync > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.log" \
         || { tail -30 "$OUT/bench_prof.log"; exit 1; } ;;
     probe)
       timeout -k 10 180 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
@@ -26,7 +26,7 @@ for step in "$@"; do
         || { tail -30 "$OUT/rccl_probe.log"; echo "probe failed (continuing)"; } ;;
     bench2)
       NBG_SAME_DEVICE=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-        --master-addr 127.0.0.1 --master-port 29513 bench.py --gpus 2 --steps 2 --warmup 1 --scale 20 \
+        --master-addr 127.0.0.1 --master-port 29513 bench.py --full --gpus 2 --steps 2 --warmup 1 --scale 20 \
         > "$OUT/bench2.json" 2> "$OUT/bench2.log" || { tail -30 "$OUT/bench2.log"; exit 1; } ;;
     pmc)
       for c in FETCH_SIZE WRITE_SIZE; do

@@ -2,7 +2,7 @@
 # Named GPU-box steps (from the repo root, via gpurun): bash tools/gpu_steps.sh <tag> <step>...
 # (The one-off round scripts of rounds 1-5 are folded into these steps; tools/gpu_run.sh runs
 # ad-hoc '<name>|<seconds>|<command>' steps the same way.)
-#   tests  — pytest -m gpu;  smoke — __graft_entry__.smoke();  bench — default bench.py;
+#   tests  — pytest -m gpu;  smoke — __graft_entry__.smoke();  bench — bench.py --full;
 #   load26 — RMAT-26 generate + load + GO leg only (load time);  prof26 — kernel trace of the bench;
 #   pmc26 / pmc22 / sq26 — GO HBM / SQ counters;  pmcsp — SHORTEST (rolling + one-pair) HBM and SQ
 #   counters;  pmcc5 — C5 GO 4 STEPS HBM counters and kernel trace;  bench8 — 8-rank rehearsal
@@ -65,11 +65,11 @@ for step in "$@"; do
         python3 -u tools/c5_probe.py 24 2 > "$OUT/profc5.txt" 2>&1 || { tail -30 "$OUT/profc5.txt"; exit 1; } ;;
     prof26)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof26" -o run --output-format csv -- \
-        python3 -u bench.py --sp-pairs 2000 --no-cpu-baseline --verify 0 --c2 0 --c5-scale 0 --getbound-reqs 0 --c1-reqs 0 \
+        python3 -u bench.py --full --sp-pairs 2000 --no-cpu-baseline --verify 0 --c2 0 --c5-scale 0 --getbound-reqs 0 --c1-reqs 0 \
         > "$OUT/bench_prof26.json" 2> "$OUT/bench_prof26.log" || { tail -30 "$OUT/bench_prof26.log"; exit 1; } ;;
     go26|go26flags)
       [ "$step" = go26flags ] && export NBG_MARK_FLAGS=1
-      timeout -k 10 600 python -u bench.py --sp-pairs 0 --no-cpu-baseline --verify 4 --c2 0 --c5-scale 0 \
+      timeout -k 10 600 python -u bench.py --full --sp-pairs 0 --no-cpu-baseline --verify 4 --c2 0 --c5-scale 0 \
         --getbound-reqs 0 > "$OUT/$step.json" 2> "$OUT/$step.log" || { tail -30 "$OUT/$step.log"; exit 1; }
       unset NBG_MARK_FLAGS ;;
     anat26)   # GO 3 STEPS per-query anatomy, kernel-traced
@@ -81,7 +81,7 @@ for step in "$@"; do
       timeout -k 10 700 bash tools/go_ab.sh "$TAG/wakeab" nebula_amd/libnbg.so nebula_amd/libnbg.so,NBG_WAKE=event \
         > "$OUT/wakeab.txt" 2>&1 || { tail -30 "$OUT/wakeab.txt"; exit 1; }
       for wk in flag event; do
-        NBG_WAKE=$wk timeout -k 10 400 python -u bench.py --scale 16 --roots 4 --steps 1 --warmup 1 --sp-pairs 0 \
+        NBG_WAKE=$wk timeout -k 10 400 python -u bench.py --full --scale 16 --roots 4 --steps 1 --warmup 1 --sp-pairs 0 \
           --c2 0 --c5-scale 0 --c1-reqs 3000 --getbound-reqs 2000 --verify 0 --no-profile --no-cpu-baseline \
           > "$OUT/small_$wk.json" 2> "$OUT/small_$wk.log" || { tail -30 "$OUT/small_$wk.log"; exit 1; }
       done ;;
@@ -94,7 +94,7 @@ for step in "$@"; do
     smallab)   # the small legs: this build vs nebula_amd/libnbg_prev.so, two rounds
       for round in 1 2; do
         for lib in libnbg libnbg_prev; do
-          NBG_LIB=$PWD/nebula_amd/$lib.so NBG_GN_TRACE=1 timeout -k 10 400 python -u bench.py --scale 16 --roots 4 --steps 1 \
+          NBG_LIB=$PWD/nebula_amd/$lib.so NBG_GN_TRACE=1 timeout -k 10 400 python -u bench.py --full --scale 16 --roots 4 --steps 1 \
             --warmup 1 --sp-pairs 0 --c2 0 --c5-scale 0 --c1-reqs 3000 --getbound-reqs 2000 --verify 0 --no-profile \
             --no-cpu-baseline > "$OUT/small_${lib}_r$round.json" 2> "$OUT/small_${lib}_r$round.log" \
             || { tail -30 "$OUT/small_${lib}_r$round.log"; exit 1; }
@@ -104,7 +104,7 @@ for step in "$@"; do
     gnteam)   # getBound: the encoding team size (NBG_GN_THREADS), two rounds
       for round in 1 2; do
         for tm in 0 2 4 8; do
-          NBG_GN_THREADS=$tm NBG_GN_TRACE=1 timeout -k 10 400 python -u bench.py --scale 16 --roots 4 --steps 1 \
+          NBG_GN_THREADS=$tm NBG_GN_TRACE=1 timeout -k 10 400 python -u bench.py --full --scale 16 --roots 4 --steps 1 \
             --warmup 1 --sp-pairs 0 --c2 0 --c5-scale 0 --c1-reqs 0 --getbound-reqs 2000 --verify 0 --no-profile \
             --no-cpu-baseline > "$OUT/gn_t${tm}_r$round.json" 2> "$OUT/gn_t${tm}_r$round.log" \
             || { tail -30 "$OUT/gn_t${tm}_r$round.log"; exit 1; }
@@ -120,7 +120,7 @@ for step in "$@"; do
         --timeout-method thread > "$OUT/pytest_path.log" 2>&1 || { tail -40 "$OUT/pytest_path.log"; exit 1; } ;;
     sp26|sp26host)
       [ "$step" = sp26host ] && export NBG_SP_MODE=host
-      timeout -k 10 600 python -u bench.py --steps 1 --warmup 1 --no-profile --no-cpu-baseline --verify 4 --c2 0 \
+      timeout -k 10 600 python -u bench.py --full --steps 1 --warmup 1 --no-profile --no-cpu-baseline --verify 4 --c2 0 \
         --c5-scale 0 --getbound-reqs 0 > "$OUT/$step.json" 2> "$OUT/$step.log" || { tail -30 "$OUT/$step.log"; exit 1; }
       unset NBG_SP_MODE ;;
     probe22|probe26)
@@ -139,12 +139,12 @@ for step in "$@"; do
       timeout -k 10 1100 bash tools/sp_ab.sh "$TAG/spgrid" nebula_amd/libnbg.so nebula_amd/libnbg.so,NBG_SP_GRID=128 \
         nebula_amd/libnbg.so,NBG_SP_GRID=512 > "$OUT/spgrid.txt" 2>&1 || { tail -30 "$OUT/spgrid.txt"; exit 1; } ;;
     small)   # the small-request legs (C1 nba, getBound) with the getBound phase trace
-      NBG_GN_TRACE=1 timeout -k 10 400 python -u bench.py --scale 16 --roots 4 --steps 1 --warmup 1 --sp-pairs 0 \
+      NBG_GN_TRACE=1 timeout -k 10 400 python -u bench.py --full --scale 16 --roots 4 --steps 1 --warmup 1 --sp-pairs 0 \
         --c2 0 --c5-scale 0 --c1-reqs 3000 --getbound-reqs 2000 --verify 0 --no-profile \
         > "$OUT/small.json" 2> "$OUT/small.log" || { tail -30 "$OUT/small.log"; exit 1; } ;;
     smallprof)   # kernel trace of the small-request legs
       timeout -k 10 400 rocprofv3 --kernel-trace --stats -d "$OUT/smallprof" -o run --output-format csv -- \
-        python3 -u bench.py --scale 16 --roots 4 --steps 1 --warmup 1 --sp-pairs 0 --c2 0 --c5-scale 0 \
+        python3 -u bench.py --full --scale 16 --roots 4 --steps 1 --warmup 1 --sp-pairs 0 --c2 0 --c5-scale 0 \
         --c1-reqs 2000 --getbound-reqs 2000 --verify 0 --no-profile --no-cpu-baseline \
         > "$OUT/smallprof.json" 2> "$OUT/smallprof.log" || { tail -30 "$OUT/smallprof.log"; exit 1; } ;;
     p8)   # the 8-way partition, in-process ranks on one GPU
@@ -155,7 +155,7 @@ for step in "$@"; do
         --master-port 29511 tools/rccl_probe.py --same-device > "$OUT/rccl8_probe.log" 2>&1 \
         || { tail -40 "$OUT/rccl8_probe.log"; exit 1; } ;;
     bench8)   # 8-rank bench rehearsal on one GPU (RMAT-20, socket transport)
-      NBG_SAME_DEVICE=1 timeout -k 10 900 python -u bench.py --gpus 8 --scale 20 --sp-pairs 2000 --steps 3 --warmup 1 \
+      NBG_SAME_DEVICE=1 timeout -k 10 900 python -u bench.py --full --gpus 8 --scale 20 --sp-pairs 2000 --steps 3 --warmup 1 \
         > "$OUT/bench8_rmat20_same_device.json" 2> "$OUT/bench8.log" || { tail -40 "$OUT/bench8.log"; exit 1; } ;;
     diagnba)   # FindPathTest goldens over 8 / 7 in-process ranks, per case and mode
       NBG_COMM_TIMEOUT_S=60 timeout -k 10 300 python -u tools/diag_nba_paths.py 8 7 > "$OUT/diag_nba_paths.txt" 2>&1 \
@@ -166,7 +166,7 @@ for step in "$@"; do
       NBG_COMM_TIMEOUT_S=${NBG_COMM_TIMEOUT_S:-60} timeout -k 10 900 python -u -m pytest "$t" -x -v --timeout 150 --timeout-method thread \
         > "$OUT/pytest_$n.log" 2>&1 || { tail -40 "$OUT/pytest_$n.log"; exit 1; } ;;
     bench)
-      timeout -k 10 900 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.log" || { tail -30 "$OUT/bench.log"; exit 1; } ;;
+      timeout -k 10 900 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.log" || { tail -30 "$OUT/bench.log"; exit 1; } ;;
   esac
   echo "step $step done"
 done
