@@ -17,6 +17,8 @@
  *   nbg_go_prepare / _execute  ≙ GoExecutor::prepare() / execute() (GoExecutor.cpp:28-110)
  *   nbg_find_path              ≙ FindPathExecutor result semantics
  *       (src/graph/FindPathExecutor.cpp:145-715)
+ *   nbg_group_by               ≙ GroupByExecutor (src/graph/GroupByExecutor.cpp:181-322,
+ *       AggregateFunction.h)
  *   nbg_get_neighbors          ≙ StorageServiceHandler::future_getBound → QueryBoundProcessor
  *       (src/storage/StorageServiceHandler.cpp:33-40, src/storage/QueryBoundProcessor.cpp:16-220)
  */
@@ -31,6 +33,7 @@ extern "C" {
 
 /* ---- status codes (storage.thrift ErrorCode / graph.thrift ErrorCode values) ---------- */
 #define NBG_OK                     0
+#define NBG_E_SYNTAX_ERROR        (-7)    /* graph.thrift E_SYNTAX_ERROR */
 #define NBG_E_EXECUTION_ERROR     (-8)    /* graph E_EXECUTION_ERROR: eval error in WHERE/YIELD */
 #define NBG_E_PART_NOT_FOUND      (-14)
 #define NBG_E_EDGE_PROP_NOT_FOUND (-21)
@@ -53,6 +56,17 @@ extern "C" {
  *   GO, FIND PATH, GetNeighbors); a WHERE + YIELD program over 256 instructions or 16 live
  *   registers per OVER type; GO over 32 STEPS; FIND SHORTEST PATH UPTO over 63, FIND ALL PATH
  *   UPTO over 32; $$ of a tag registered 17th or later; more than 32 $- / $var input columns.
+ * nbg_group_by (tests/test_gpu_groupby.py holds one test per limit a GO result can reach; the last
+ * two and the mixed-kind column are guards no GO result reaches today):
+ *   a group or yield expression that is neither a bare `$-.col' nor constant-foldable;
+ *   a referenced input column whose value kind differs between OVER types (col_kind == -1);
+ *   an input whose row schema re-reads its columns (a misaligned or FLOAT column);
+ *   AVG over a VID or TIMESTAMP column (the reference reads the wrong union member there);
+ *   MAX / MIN over a string column that can hold strings outside the dictionary;
+ *   more than NBG_MAX_YIELDS group columns or yield columns;
+ *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
+ *   a carried-over string column whose OVER types spell different constants outside the dictionary;
+ *   2^32 groups or more (group ids are 32 bits).
  * (A storage filter with a function call is E_INVALID_FILTER per part, as checkExp answers it,
  * QueryBaseProcessor.inl:172-290.)
  * Not limits: $- / $var input strings absent from the snapshot's dictionary, string functions
@@ -290,6 +304,70 @@ int32_t nbg_rows_segment(const nbg_rows* r, int64_t i, uint64_t* begin, uint64_t
  * index (nbg_rows_string) for host rows. */
 int32_t nbg_rows_digest(const nbg_rows* r, uint64_t* out);
 void nbg_rows_free(nbg_rows* r);
+
+/* ---- GROUP BY over a device-resident GO result (GroupByExecutor semantics) ----------------
+ * `| GROUP BY $-.x YIELD $-.x, COUNT(*), SUM($-.w) ...` over the rows a GO left in HBM, so a
+ * caller need not fetch them to aggregate on the CPU (GroupByExecutor.cpp:226-322).
+ * Input: a device-resident result of the same single engine (nbg_go_device, nbg_go_execute with
+ * device = 1, nbg_go_wait); it stays valid and unchanged.  A host-only result is
+ * NBG_E_INVALID_ARGUMENT.  Output: an ordinary device-resident nbg_rows of one segment, one row
+ * per group; every nbg_rows_* accessor works on it and it spells its strings as `in` does
+ * (dictionary codes, constants, derived codes).  The call runs under the engine lock on the
+ * engine's stream; its scratch (tables, accumulators) is released before it returns.
+ *
+ * Zero input rows: NBG_OK and a zero-row result, with no check at all (execute() returns before
+ * checkAll, GroupByExecutor.cpp:184-188).  Otherwise NBG_E_SYNTAX_ERROR (prepareYield,
+ * prepareGroup, checkAll, :44-178) for: an empty group or yield list; a group column that is an
+ * aggregate call (the request has no function field for group columns: a FunctionCall named like
+ * an aggregate stands for it); "*" under anything but COUNT / COUNT_DISTINCT; a group column
+ * that is neither `$-.name' of the input, nor a function call, nor a bare name (a string primary)
+ * equal to the alias of a yield column that is itself `$-.name' (that column is then the key);
+ * a yield `$-.name' absent from the input, or without a function and not among the `$-' group
+ * keys; a `$var' yield.  A constant expression that fails to evaluate is
+ * NBG_E_EXECUTION_ERROR.  Device scope: see "Device limits" (NBG_E_UNSUPPORTED; the caller then
+ * runs the reference's loop over the fetched rows).
+ *
+ * Group identity: the key cells' payloads (the kinds are uniform per column).  Double keys -0.0
+ * and 0.0 are one group (ColumnValue::operator==, std::hash<double>); which sign is reported is
+ * unspecified.  NaN keys group by their bits — the reference makes every NaN row its own group.
+ * Constant keys add nothing: with only constant keys there is one group.
+ * Functions, by the input column's NBG_T_* type (constants carry their own kind):
+ *   NONE   the key cell (or the constant);            COUNT  rows of the group (COUNT(*) alike)
+ *   COUNT_DISTINCT  distinct payloads within the group (a constant: 1)
+ *   SUM    INT / VID / TIMESTAMP: int64, wrapping, the column's type; DOUBLE: double; else INT 0
+ *   AVG    INT: double(sum) / count; DOUBLE: sum / count; BOOL / STRING: 0.0
+ *   MAX / MIN  the column's own order and type: signed int64, IEEE doubles, false < true,
+ *          dictionary strings by their sorted-dictionary codes
+ *   STD    INT / DOUBLE: sqrt(sum((x - avg)^2) / n), DOUBLE; else INT 0
+ *   BIT_AND / BIT_OR / BIT_XOR  INT columns and int constants; else INT 0
+ * Result column kinds follow those rules (generateOutputSchema, :355-391).  Row order is
+ * unspecified (the reference's is unordered_map iteration order).  A double SUM, AVG or STD adds
+ * its terms in another order than the reference's row order, so it can differ in the last bits
+ * (and between two calls); the final division and square root are IEEE-exact.
+ * Single engine only: merging the ranks' rows of a partitioned engine is a later change. */
+#define NBG_AGG_NONE           0   /* plain column */
+#define NBG_AGG_COUNT          1
+#define NBG_AGG_COUNT_DISTINCT 2
+#define NBG_AGG_SUM            3
+#define NBG_AGG_AVG            4
+#define NBG_AGG_MAX            5
+#define NBG_AGG_MIN            6
+#define NBG_AGG_STD            7
+#define NBG_AGG_BIT_AND        8
+#define NBG_AGG_BIT_OR         9
+#define NBG_AGG_BIT_XOR        10
+typedef struct {
+  const char* const* input_names;        /* names of `in`'s columns (nbg_rows carries none)      */
+  const uint8_t* const* group_exprs;     /* Expression::encode bytes per GROUP BY column          */
+  const uint32_t* group_lens;
+  int32_t num_groups;
+  const uint8_t* const* yield_exprs;     /* ... per YIELD column (COUNT(*): the string primary "*") */
+  const uint32_t* yield_lens;
+  const int32_t* yield_funs;             /* NBG_AGG_* per YIELD column                             */
+  const char* const* yield_aliases;      /* AS name or NULL (the array itself may be NULL)         */
+  int32_t num_yields;
+} nbg_group_request;
+int32_t nbg_group_by(nbg_engine* e, const nbg_rows* in, const nbg_group_request* req, nbg_rows** out);
 
 /* ---- FIND SHORTEST | ALL PATH (FindPathExecutor semantics) ----------------------------- */
 typedef struct {

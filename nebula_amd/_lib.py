@@ -16,6 +16,7 @@ P = C.POINTER
 
 # status codes (nbg.h)
 OK = 0
+E_SYNTAX_ERROR = -7
 E_EXECUTION_ERROR = -8
 E_PART_NOT_FOUND = -14
 E_EDGE_PROP_NOT_FOUND = -21
@@ -32,6 +33,12 @@ FAULT_ALLOC = 1      # nbg_inject_fault sites (include/nbg.h)
 V_INT, V_DOUBLE, V_BOOL, V_STRING = 0, 1, 2, 3   # NBG_V_* value kinds
 FAULT_DEVICE = 2
 FAULT_STREAM = 3
+# NBG_AGG_* (nbg_group_request.yield_funs)
+AGG_NONE, AGG_COUNT, AGG_COUNT_DISTINCT, AGG_SUM, AGG_AVG, AGG_MAX, AGG_MIN = 0, 1, 2, 3, 4, 5, 6
+AGG_STD, AGG_BIT_AND, AGG_BIT_OR, AGG_BIT_XOR = 7, 8, 9, 10
+AGG_BY_NAME = {"": AGG_NONE, "COUNT": AGG_COUNT, "COUNT_DISTINCT": AGG_COUNT_DISTINCT, "SUM": AGG_SUM,
+               "AVG": AGG_AVG, "MAX": AGG_MAX, "MIN": AGG_MIN, "STD": AGG_STD, "BIT_AND": AGG_BIT_AND,
+               "BIT_OR": AGG_BIT_OR, "BIT_XOR": AGG_BIT_XOR}
 
 
 class nbg_config(C.Structure):
@@ -78,6 +85,12 @@ class nbg_gn_request(C.Structure):
                 ("return_columns", P(nbg_prop_def)), ("num_return_columns", i32)]
 
 
+class nbg_group_request(C.Structure):
+    _fields_ = [("input_names", P(C.c_char_p)), ("group_exprs", P(P(u8))), ("group_lens", P(u32)),
+                ("num_groups", i32), ("yield_exprs", P(P(u8))), ("yield_lens", P(u32)), ("yield_funs", P(i32)),
+                ("yield_aliases", P(C.c_char_p)), ("num_yields", i32)]
+
+
 # (name, restype, argtypes) for every symbol include/nbg.h declares
 SIGNATURES = [
     ("nbg_create", i32, [P(nbg_config), P(vp)]),
@@ -115,6 +128,7 @@ SIGNATURES = [
     ("nbg_rows_segment", i32, [vp, i64, P(u64), P(u64)]),
     ("nbg_rows_digest", i32, [vp, P(u64)]),
     ("nbg_rows_free", None, [vp]),
+    ("nbg_group_by", i32, [vp, vp, P(nbg_group_request), P(vp)]),
     ("nbg_find_path", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_submit", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_wait", i32, [vp, P(vp)]),

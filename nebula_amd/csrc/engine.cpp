@@ -2036,6 +2036,338 @@ void nbg_rows_free(nbg_rows* r) {
   delete r;
 }
 
+// ============================================================================= GROUP BY
+// GroupByExecutor (src/graph/GroupByExecutor.cpp:44-178 the checks, :226-322 the grouping,
+// :355-391 the result schema) over a device-resident result; the kernels are in groupby.hip.
+namespace {
+
+bool gb_only_constants(const Node& n) {   // no prop, input or variable reference anywhere
+  switch (n.kind) {
+    case EK_PRIMARY: case EK_FUNC: case EK_UNARY: case EK_CAST: case EK_ARITH: case EK_REL: case EK_LOGIC: break;
+    default: return false;
+  }
+  for (auto& k : n.kids)
+    if (!k || !gb_only_constants(*k)) return false;
+  return true;
+}
+
+bool gb_is_agg_name(std::string f) {
+  for (char& ch : f) ch = (char)toupper((unsigned char)ch);
+  for (const char* a : {"COUNT", "COUNT_DISTINCT", "SUM", "AVG", "MAX", "MIN", "STD", "BIT_AND", "BIT_OR", "BIT_XOR"})
+    if (f == a) return true;
+  return false;
+}
+
+// PrimaryExpression::toString of a constant (what a bare name in GROUP BY is compared to)
+std::string gb_primary_string(const Node& n) {
+  if (n.kind != EK_PRIMARY) return std::string("\x01");   // (never an alias)
+  switch (n.prim.index()) {
+    case 0: return std::to_string(std::get<0>(n.prim));
+    case 1: return std::to_string(std::get<1>(n.prim));
+    case 2: return std::get<2>(n.prim) ? "true" : "false";
+    default: return std::get<3>(n.prim);
+  }
+}
+
+int32_t gb_natural_type(VKind k) {
+  return k == VK_DOUBLE ? NBG_T_DOUBLE : k == VK_BOOL ? NBG_T_BOOL : k == VK_STRING ? NBG_T_STRING : NBG_T_INT;
+}
+
+struct GbValue {          // a YIELD operand: an input column or a constant
+  int col = -1;
+  VKind kind = VK_INT;
+  int32_t type = NBG_T_INT;
+  int64_t bits = 0;       // constant payload (strings: the dictionary code)
+  std::string text;       // constant string
+};
+
+nbg_rows* gb_new_rows(Engine& E, int ncols) {
+  auto* r = new nbg_rows();
+  r->eng = &E;
+  r->ncols = ncols;
+  r->on_device = true;
+  r->kinds.emplace_back(ncols, VK_INT);
+  r->const_str.emplace_back(ncols, std::string());
+  r->col_types.assign(ncols, NBG_T_INT);
+  r->wclass.emplace_back(ncols, (uint8_t)W_ID);
+  return r;
+}
+
+}  // namespace
+
+int32_t nbg_group_by(nbg_engine* h, const nbg_rows* in, const nbg_group_request* rq, nbg_rows** out) {
+  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  if (in->eng != &E) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: the rows belong to another engine");
+  if (!in->on_device) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: the rows are host-only (not a device result)");
+  if (E.partitioned())
+    return E.fail(NBG_E_UNSUPPORTED, "GROUP BY on a partitioned engine (its rows live on several ranks)");
+  const int ng = rq->num_groups, ny = rq->num_yields;
+  if (!in->count) {   // GroupByExecutor::execute returns before checkAll: no check, no rows
+    *out = gb_new_rows(E, std::max(0, std::min(ny, (int)MAX_YIELDS)));
+    return NBG_OK;
+  }
+  if ((ng > 0 && (!rq->group_exprs || !rq->group_lens)) ||
+      (ny > 0 && (!rq->yield_exprs || !rq->yield_lens || !rq->yield_funs)) || !rq->input_names)
+    return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: null argument");
+  if (ng > MAX_YIELDS || ny > MAX_YIELDS)
+    return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: more than NBG_MAX_YIELDS group or yield columns");
+  std::vector<std::string> names;
+  for (int c = 0; c < in->ncols; ++c) {
+    if (!rq->input_names[c]) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: null input column name");
+    names.emplace_back(rq->input_names[c]);
+  }
+  auto find_col = [&](const std::string& n) {
+    auto it = std::find(names.begin(), names.end(), n);
+    return it == names.end() ? -1 : (int)(it - names.begin());
+  };
+  auto decode = [&](const uint8_t* p, uint32_t n, std::unique_ptr<Node>* node) -> int32_t {
+    std::string err;
+    if (!p || !n) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: an empty expression");
+    *node = decode_expr(p, n, &err);
+    return *node ? NBG_OK : E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: " + err);
+  };
+  // ---- prepareYield / prepareGroup / checkAll
+  if (ny <= 0) return E.fail(NBG_E_SYNTAX_ERROR, "Yield cols is empty");
+  std::vector<std::unique_ptr<Node>> ynodes(ny), gnodes(std::max(ng, 0));
+  std::map<std::string, int> aliases;   // alias -> the first `$-.x AS alias` yield
+  for (int y = 0; y < ny; ++y) {
+    if (int32_t rc = decode(rq->yield_exprs[y], rq->yield_lens[y], &ynodes[y])) return rc;
+    const int32_t f = rq->yield_funs[y];
+    if (f < NBG_AGG_NONE || f > NBG_AGG_BIT_XOR) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: unknown function");
+    const Node& n = *ynodes[y];
+    const bool star = n.kind == EK_PRIMARY && n.prim.index() == 3 && std::get<3>(n.prim) == "*";
+    if (star && f != NBG_AGG_COUNT && f != NBG_AGG_COUNT_DISTINCT) return E.fail(NBG_E_SYNTAX_ERROR, "Syntax error: near `*'");
+    const char* al = rq->yield_aliases ? rq->yield_aliases[y] : nullptr;
+    if (al && n.kind == EK_INPUT) aliases.emplace(al, y);
+  }
+  if (ng <= 0) return E.fail(NBG_E_SYNTAX_ERROR, "Group cols is empty");
+  std::set<int> key_set;          // the `$-` group keys (input columns)
+  std::vector<int> key_cols;
+  for (int g = 0; g < ng; ++g) {
+    if (int32_t rc = decode(rq->group_exprs[g], rq->group_lens[g], &gnodes[g])) return rc;
+    const Node& n = *gnodes[g];
+    if (n.kind == EK_FUNC && gb_is_agg_name(n.alias))
+      return E.fail(NBG_E_SYNTAX_ERROR, "Use invalid group function `" + n.alias + "'");
+  }
+  for (int g = 0; g < ng; ++g) {
+    const Node& n = *gnodes[g];
+    if (n.kind == EK_INPUT) {
+      const int c = find_col(n.prop);
+      if (c < 0) return E.fail(NBG_E_SYNTAX_ERROR, "Group `" + n.prop + "' isn't in output fields");
+      if (key_set.insert(c).second) key_cols.push_back(c);
+      continue;
+    }
+    if (n.kind == EK_FUNC) continue;   // (constant-folded below)
+    const std::string gname = gb_primary_string(n);
+    auto a = aliases.find(gname);
+    if (a == aliases.end()) return E.fail(NBG_E_SYNTAX_ERROR, "Group `" + gname + "' isn't in output fields");
+    const int c = find_col(ynodes[a->second]->prop);   // (absent: the yield check below answers)
+    if (c >= 0 && key_set.insert(c).second) key_cols.push_back(c);
+  }
+  for (int y = 0; y < ny; ++y) {
+    const Node& n = *ynodes[y];
+    if (n.kind == EK_INPUT) {
+      const int c = find_col(n.prop);
+      if (c < 0) return E.fail(NBG_E_SYNTAX_ERROR, "Yield `" + n.prop + "' isn't in output fields");
+      if (rq->yield_funs[y] == NBG_AGG_NONE && !key_set.count(c))
+        return E.fail(NBG_E_SYNTAX_ERROR, "Yield `" + n.prop + "' isn't in group fields");
+    } else if (n.kind == EK_VAR) {
+      return E.fail(NBG_E_SYNTAX_ERROR, "Can't support variableExpression");
+    }
+  }
+  // ---- device scope
+  if (in->misaligned || in->float_col)
+    return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  static const std::vector<int32_t> no_over;
+  CompileEnv cenv{};
+  cenv.etype = 0;
+  cenv.over = &no_over;
+  cenv.edges = &E.edges;
+  cenv.strings = &E.snap.strings;
+  cenv.tags = &E.tags;
+  auto constant = [&](const Node& n, GbValue* v) -> int32_t {
+    if (!gb_only_constants(n)) return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: an expression that is neither `$-.col' nor constant");
+    ProgramBuilder pb;
+    Compiled c;
+    std::string err;
+    const int32_t rc = compile_expr(n, cenv, pb, &c, &err, true);
+    if (rc) return E.fail(rc, "GROUP BY: " + err);
+    if (c.always_error) return E.fail(NBG_E_EXECUTION_ERROR, "GROUP BY: a constant expression fails to evaluate");
+    if (!c.is_const || c.derived) return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: an expression that is not constant");
+    v->col = -1;
+    v->kind = c.kind;
+    v->type = gb_natural_type(c.kind);
+    v->bits = c.const_bits;
+    v->text = c.const_str;
+    return NBG_OK;
+  };
+  auto column = [&](int c, GbValue* v) -> int32_t {
+    if (in->col_kind(c) < 0) return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: column `" + names[c] + "' mixes value kinds");
+    v->col = c;
+    v->kind = (VKind)in->col_kind(c);
+    v->type = c < (int)in->col_types.size() && in->col_types[c] ? in->col_types[c] : gb_natural_type(v->kind);
+    return NBG_OK;
+  };
+  // a string column the result carries over: what spells its codes outside the dictionary
+  auto column_const_str = [&](int c, std::string* s) -> int32_t {
+    bool have = false;
+    for (auto& cs : in->const_str) {
+      if ((int)cs.size() <= c) continue;
+      if (have && *s != cs[c])
+        return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: column `" + names[c] + "' spells different constants per OVER type");
+      *s = cs[c];
+      have = true;
+    }
+    return NBG_OK;
+  };
+  for (int g = 0; g < ng; ++g) {   // a function-call key must fold: it adds nothing to the identity
+    if (gnodes[g]->kind != EK_FUNC) continue;
+    GbValue v;
+    if (int32_t rc = constant(*gnodes[g], &v)) return rc;
+  }
+  GbPlan plan;
+  plan.nkeys = (int)key_cols.size();
+  for (int k = 0; k < plan.nkeys; ++k) {
+    GbValue v;
+    if (int32_t rc = column(key_cols[k], &v)) return rc;
+    plan.key_col[k] = (int8_t)key_cols[k];
+    plan.key_dbl[k] = v.kind == VK_DOUBLE;
+  }
+  plan.acc[0] = GbAcc{GB_COUNT, 0, -1, 0, 0};
+  plan.nacc = 1;
+  plan.nout = ny;
+  std::unique_ptr<nbg_rows> res(gb_new_rows(E, ny));
+  auto slot = [&](GbOp op, const GbValue& v, int ref) {
+    plan.acc[plan.nacc] = GbAcc{(uint8_t)op, (uint8_t)(v.kind == VK_DOUBLE), (int8_t)v.col, (uint8_t)ref, v.bits};
+    return plan.nacc++;
+  };
+  for (int y = 0; y < ny; ++y) {
+    GbValue v;
+    const Node& n = *ynodes[y];
+    if (n.kind == EK_INPUT) {
+      if (int32_t rc = column(find_col(n.prop), &v)) return rc;
+    } else if (int32_t rc = constant(n, &v)) {
+      return rc;
+    }
+    GbOut& o = plan.out[y];
+    VKind okind = VK_INT;
+    int32_t otype = NBG_T_INT;
+    auto emit_const = [&](VKind k, int32_t t, int64_t bits) {
+      o = GbOut{GE_CONST, -1, 0, bits};
+      okind = k;
+      otype = t;
+    };
+    const bool int_like = v.type == NBG_T_INT || v.type == NBG_T_VID || v.type == NBG_T_TIMESTAMP;
+    const bool is_dbl = v.type == NBG_T_DOUBLE;
+    const double zero = 0.0;
+    int64_t zero_bits;
+    memcpy(&zero_bits, &zero, 8);
+    switch (rq->yield_funs[y]) {
+      case NBG_AGG_NONE:   // Group::apply keeps the row's value: a key cell or the constant
+        if (v.col >= 0) {
+          o = GbOut{GE_KEY, (int8_t)v.col, 0, 0};
+          okind = v.kind;
+          otype = v.type;
+          if (v.kind == VK_STRING)
+            if (int32_t rc = column_const_str(v.col, &res->const_str[0][y])) return rc;
+        } else {
+          emit_const(v.kind, v.type, v.bits);
+          res->const_str[0][y] = v.text;
+        }
+        break;
+      case NBG_AGG_COUNT:
+        o = GbOut{GE_SLOT, -1, 0, 0};
+        break;
+      case NBG_AGG_COUNT_DISTINCT:
+        if (v.col < 0) emit_const(VK_INT, NBG_T_INT, 1);
+        else o = GbOut{GE_SLOT, -1, (uint8_t)slot(GB_DISTINCT, v, 0), 0};
+        break;
+      case NBG_AGG_SUM:
+        if (int_like) {
+          o = GbOut{GE_SLOT, -1, (uint8_t)slot(GB_SUM_I, v, 0), 0};
+          otype = v.type;
+        } else if (is_dbl) {
+          o = GbOut{GE_SLOT, -1, (uint8_t)slot(GB_SUM_D, v, 0), 0};
+          okind = VK_DOUBLE;
+          otype = NBG_T_DOUBLE;
+        } else {
+          emit_const(VK_INT, NBG_T_INT, 0);
+        }
+        break;
+      case NBG_AGG_AVG:
+        okind = VK_DOUBLE;
+        otype = NBG_T_DOUBLE;
+        if (v.type == NBG_T_VID || v.type == NBG_T_TIMESTAMP)
+          return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: AVG over a VID or TIMESTAMP column");
+        if (int_like) o = GbOut{GE_AVG_I, -1, (uint8_t)slot(GB_SUM_I, v, 0), 0};
+        else if (is_dbl) o = GbOut{GE_AVG_D, -1, (uint8_t)slot(GB_SUM_D, v, 0), 0};
+        else emit_const(VK_DOUBLE, NBG_T_DOUBLE, zero_bits);
+        break;
+      case NBG_AGG_MAX: case NBG_AGG_MIN: {
+        okind = v.kind;
+        otype = v.type;
+        if (v.col < 0) {
+          emit_const(v.kind, v.type, v.bits);
+          res->const_str[0][y] = v.text;
+          break;
+        }
+        if (v.kind == VK_STRING) {
+          bool outside = !in->derived.empty();
+          for (auto& cs : in->const_str) outside = outside || ((int)cs.size() > v.col && !cs[v.col].empty());
+          if (outside)
+            return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: MAX/MIN over a string column that can hold strings outside the dictionary");
+        }
+        const GbOp op = rq->yield_funs[y] == NBG_AGG_MAX ? GB_MAX : GB_MIN;
+        o = GbOut{(uint8_t)(v.kind == VK_DOUBLE ? GE_ORD_D : GE_ORD_I), -1, (uint8_t)slot(op, v, 0), 0};
+        break;
+      }
+      case NBG_AGG_STD:
+        if (v.type == NBG_T_INT || is_dbl) {
+          const int s = slot(is_dbl ? GB_SUM_D : GB_SUM_I, v, 0);
+          o = GbOut{GE_STD, -1, (uint8_t)slot(GB_SQ, v, s), 0};
+          okind = VK_DOUBLE;
+          otype = NBG_T_DOUBLE;
+        } else {
+          emit_const(VK_INT, NBG_T_INT, 0);
+        }
+        break;
+      default: {   // BIT_AND / BIT_OR / BIT_XOR: INT values only
+        if (v.type != NBG_T_INT) { emit_const(VK_INT, NBG_T_INT, 0); break; }
+        const GbOp op = rq->yield_funs[y] == NBG_AGG_BIT_AND ? GB_AND : rq->yield_funs[y] == NBG_AGG_BIT_OR ? GB_OR : GB_XOR;
+        o = GbOut{GE_SLOT, -1, (uint8_t)slot(op, v, 0), 0};
+      }
+    }
+    res->kinds[0][y] = okind;
+    res->col_types[y] = otype;
+  }
+  // ---- the passes
+  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+  auto* m = const_cast<nbg_rows*>(in);
+  m->build_segs();
+  std::vector<std::pair<uint64_t, uint64_t>> segs;
+  for (auto& sg : m->segs) segs.emplace_back(sg.begin, sg.end - sg.begin);
+  Workspace* inw = in->owned_ws ? in->owned_ws : in->ws;
+  if (!inw) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: the rows have no device workspace");
+  Workspace* ow = nullptr;
+  uint64_t G = 0;
+  std::string err;
+  if (int32_t rc = ws_group_by(inw, E.stream, segs, plan, &ow, &G, &err)) return E.fail(rc, err);
+  res->ws = res->owned_ws = ow;
+  res->count = G;
+  res->derived = in->derived;
+  nbg_rows::TypeBlocks tb;
+  tb.region = 0;
+  tb.blk_cap = G;
+  tb.counts.assign(1, (uint32_t)G);
+  res->blocks.push_back(std::move(tb));
+  for (int c = 0; c < ny; ++c) res->dcols.push_back(ws_row_col(ow, c));
+  *out = res.release();
+  return NBG_OK;
+}
+
 int32_t nbg_set_path_replica(nbg_engine* h, int32_t mode) {
   if (!h || mode < 0 || mode > 1) return NBG_E_INVALID_ARGUMENT;
   Engine& E = h->e;

@@ -678,6 +678,57 @@ hipError_t ws_distinct(Workspace* w, const std::vector<std::array<uint64_t, 3>>&
                        const std::vector<std::vector<VKind>>& kinds, std::vector<uint32_t>* counts);
 const uint32_t* ws_current_frontier(Workspace* w);
 
+// ---- GROUP BY over device rows (groupby.hip; GroupByExecutor.cpp:226-322, AggregateFunction.h)
+// The request compiled to accumulator slots (one 8-byte cell per group each; slot 0 is always
+// the group's row count) and to one emit rule per result column.
+enum GbOp : uint8_t {
+  GB_COUNT = 0, GB_SUM_I, GB_SUM_D, GB_MAX, GB_MIN, GB_AND, GB_OR, GB_XOR,
+  GB_SQ,         // second pass: sum of (x - avg)^2, avg from slot `ref` and the count
+  GB_DISTINCT,   // third pass: distinct (group, payload) pairs
+};
+enum GbEmit : uint8_t {
+  GE_KEY = 0,    // the representative row's cell of input column `col`
+  GE_CONST,      // `bits`
+  GE_SLOT,       // the slot as it stands (counts, sums, bit folds)
+  GE_ORD_I,      // MAX / MIN of an integer-ordered column: the slot's order-preserving image back
+  GE_ORD_D,      // ... of a DOUBLE column
+  GE_AVG_I,      // double(int64 slot) / count
+  GE_AVG_D,      // double slot / count
+  GE_STD,        // sqrt(slot / count)
+};
+struct GbAcc {
+  uint8_t op;       // GbOp
+  uint8_t dbl;      // the value is a double (ordering, GB_SQ's conversion, -0.0 == 0.0 in GB_DISTINCT)
+  int8_t col;       // input column, -1: the constant `bits`
+  uint8_t ref;      // GB_SQ: the slot holding the sum (a double sum when `dbl`, else int64)
+  int64_t bits;
+};
+struct GbOut {
+  uint8_t emit;     // GbEmit
+  int8_t col;       // GE_KEY
+  uint8_t slot;
+  int64_t bits;     // GE_CONST
+};
+constexpr int GB_MAX_ACC = 2 * MAX_YIELDS + 1;
+struct GbPlan {
+  int nkeys = 0;                  // 0: constant keys only — one group, no table
+  int8_t key_col[MAX_YIELDS] = {};
+  uint8_t key_dbl[MAX_YIELDS] = {};   // a DOUBLE key column: -0.0 and 0.0 are one key
+  int nacc = 1;
+  GbAcc acc[GB_MAX_ACC] = {};
+  int nout = 0;
+  GbOut out[MAX_YIELDS] = {};
+};
+// Accumulators of at most this many bytes (slots x groups x 8) are kept in each workgroup's LDS
+// and flushed once (DESIGN.md "GROUP BY").
+constexpr uint64_t GB_LDS_BYTES = 16 * 1024;
+// Groups the rows of `inw` listed by segs (first row, rows) and writes one row per group into a
+// fresh rows-only workspace on `stream` (*outw; ws_destroy releases it).  Synchronous; every
+// scratch allocation is released before it returns.  NBG_OK, NBG_E_OUT_OF_MEMORY,
+// NBG_E_UNSUPPORTED (2^32 groups or more) or NBG_E_DEVICE (*err names the failing call).
+int32_t ws_group_by(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
+                    const GbPlan& plan, Workspace** outw, uint64_t* groups, std::string* err);
+
 // Query pipeline (all asynchronous on the workspace stream until ws_end_query):
 hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, const std::vector<TypeProgram>* progs,
                           uint64_t stmt_id);

@@ -379,6 +379,28 @@ class Engine:
         self._check(rc, "go_device")
         return DeviceRows(self, out)
 
+    def group_by(self, rows: DeviceRows, input_names, groups, yields) -> DeviceRows:
+        """nbg_group_by: ``| GROUP BY groups YIELD yields`` over a device-resident result.
+        ``input_names`` names ``rows``' columns, ``groups`` holds Expression::encode bytes per group
+        column and ``yields`` is a list of ``(fun, expr_bytes, alias)`` with ``fun`` an NBG_AGG_* value
+        or name ("" / "COUNT" / "SUM" ...) and ``alias`` a name or None.  The result is a new
+        DeviceRows; ``rows`` stays valid and unchanged."""
+        def exprs(items):
+            bufs = [np.frombuffer(bytes(b), np.uint8).copy() for b in items]
+            ptrs = (C.POINTER(C.c_uint8) * max(1, len(bufs)))(*[b.ctypes.data_as(C.POINTER(C.c_uint8)) for b in bufs])
+            lens = (C.c_uint32 * max(1, len(bufs)))(*[len(b) for b in bufs])
+            return bufs, ptrs, lens
+        names = (C.c_char_p * max(1, len(input_names)))(*[n.encode() for n in input_names])
+        gbufs, gptrs, glens = exprs(groups)
+        ybufs, yptrs, ylens = exprs([y[1] for y in yields])
+        funs = (C.c_int32 * max(1, len(yields)))(*[L.AGG_BY_NAME[y[0].upper()] if isinstance(y[0], str) else int(y[0])
+                                                   for y in yields])
+        aliases = (C.c_char_p * max(1, len(yields)))(*[y[2].encode() if y[2] is not None else None for y in yields])
+        req = L.nbg_group_request(names, gptrs, glens, len(gbufs), yptrs, ylens, funs, aliases, len(ybufs))
+        out = C.c_void_p()
+        self._check(self.lib.nbg_group_by(self.h, rows.h, C.byref(req), C.byref(out)), "group_by")
+        return DeviceRows(self, out)
+
     def default_columns(self, etypes, over_all=False):
         """Edge types of a YIELD-less GO's `<edge>._dst` columns, in column order (OVER order;
         for OVER *, the response edge_schema's iteration order, GoExecutor.cpp:481-499)."""
