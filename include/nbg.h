@@ -19,6 +19,8 @@
  *       (src/graph/FindPathExecutor.cpp:145-715)
  *   nbg_group_by               ≙ GroupByExecutor (src/graph/GroupByExecutor.cpp:181-322,
  *       AggregateFunction.h)
+ *   nbg_order_by               ≙ OrderByExecutor + LimitExecutor (src/graph/OrderByExecutor.cpp:14-155,
+ *       src/graph/LimitExecutor.cpp:18-66)
  *   nbg_get_neighbors          ≙ StorageServiceHandler::future_getBound → QueryBoundProcessor
  *       (src/storage/StorageServiceHandler.cpp:33-40, src/storage/QueryBoundProcessor.cpp:16-220)
  */
@@ -67,6 +69,16 @@ extern "C" {
  *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
  *   a carried-over string column whose OVER types spell different constants outside the dictionary;
  *   2^32 groups or more (group ids are 32 bits).
+ * nbg_order_by (tests/test_gpu_orderby.py holds one test per limit a GO result can reach; the
+ * mixed-kind column is a guard no GO result reaches today):
+ *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
+ *   an input whose row schema re-reads its columns (a misaligned or FLOAT column);
+ *   a column whose value kind differs between OVER types (col_kind == -1): a factor cannot be
+ *   ordered, and the one-segment result gives every column one kind;
+ *   a string factor column that can hold strings outside the dictionary (a non-empty derived
+ *   table, or a per-OVER-type string constant for that column);
+ *   a carried-over string column whose OVER types spell different constants outside the dictionary;
+ *   more than NBG_MAX_YIELDS factors; a result of 2^32 rows or more.
  * (A storage filter with a function call is E_INVALID_FILTER per part, as checkExp answers it,
  * QueryBaseProcessor.inl:172-290.)
  * Not limits: $- / $var input strings absent from the snapshot's dictionary, string functions
@@ -369,6 +381,52 @@ typedef struct {
 } nbg_group_request;
 int32_t nbg_group_by(nbg_engine* e, const nbg_rows* in, const nbg_group_request* req, nbg_rows** out);
 
+/* ---- ORDER BY / LIMIT over a device-resident result (OrderByExecutor, LimitExecutor) -------
+ * `| ORDER BY $-.x [ASC|DESC], ... | LIMIT [offset,] count` over rows in HBM, either clause alone
+ * or both fused (grammar: parser.yy:727-767; every factor is an InputPropertyExpression, so its
+ * name is all there is to pass).  Input and output follow nbg_group_by's contract: `in` is a
+ * device-resident result of the same single engine (a GO result, the output of nbg_group_by or of
+ * nbg_order_by itself); it stays valid and unchanged.  A host-only result, or one of another
+ * engine, is NBG_E_INVALID_ARGUMENT.  `out` is an ordinary device-resident nbg_rows of one
+ * segment whose row order (nbg_rows_fetch, the device view) is the result order; it has `in`'s
+ * columns, kinds, col_types, string constants and derived-string table, every nbg_rows_*
+ * accessor works on it and it can be fed to nbg_group_by.  The call runs under the engine lock
+ * on the engine's stream; its scratch (keys, permutations, candidates) is released before it
+ * returns.  A failed allocation is NBG_E_OUT_OF_MEMORY.
+ *
+ * Statuses, in this order: has_limit with offset < 0 or count < 0 is NBG_E_SYNTAX_ERROR
+ * (LimitExecutor::prepare, LimitExecutor.cpp:18-28), even for an empty input.  Zero input rows:
+ * NBG_OK and a zero-row result with no factor check (OrderByExecutor::beforeExecute returns
+ * before it, OrderByExecutor.cpp:137-139).  Otherwise a factor name absent from input_names is
+ * NBG_E_EXECUTION_ERROR (OrderByExecutor.cpp:140-152, OrderByTest.WrongFactor); with duplicate
+ * column names the first match wins (getFieldIndex).  Device scope: see "Device limits"
+ * (NBG_E_UNSUPPORTED; the caller then sorts the fetched rows as the reference does).
+ * LIMIT (LimitExecutor.cpp:30-66): count == 0 or rows <= offset give zero rows; otherwise the
+ * result is rows [offset, min(rows, offset + count)) of the ordered input (offset + count
+ * saturates instead of overflowing).
+ *
+ * Order (OrderByExecutor.cpp:94-131): ColumnValue::operator< per factor, later factors breaking
+ * the ties operator== leaves: signed int64 for INT / VID / TIMESTAMP; IEEE order for DOUBLE, where
+ * -0.0 and 0.0 are equal (they do not decide, the next factor does); false < true; strings by
+ * bytes — dictionary strings by their codes, which are 2 * index in the dictionary sorted by
+ * std::string::operator<, i.e. by unsigned bytes (negative codes are dictionary codes too and sort
+ * first).  DESC reverses a factor.  Rows equal under every factor come in unspecified order, and
+ * with a LIMIT which of them fall inside the window is unspecified (the reference's std::sort is
+ * not stable).  NaN factors are unspecified in the reference (they break its comparator); here
+ * they sort by their bits' IEEE total-order image.
+ * Without factors (LIMIT only) the order is the input's own segment order, the order
+ * nbg_rows_fetch delivers: limit(in, off, n) fetches exactly in's fetched rows [off, off + n).
+ * Single engine only: merging the ranks' orders of a partitioned engine is a later change. */
+typedef struct {
+  const char* const* input_names;   /* names of `in`'s columns, as in nbg_group_request          */
+  const char* const* factor_names;  /* ORDER BY factors: the `name' of `$-.name' (or bare label) */
+  const uint8_t* factor_desc;       /* per factor: 0 ASC, 1 DESC                                 */
+  int32_t num_factors;              /* 0: no ORDER BY clause (LIMIT only)                        */
+  int32_t has_limit;                /* 0: no LIMIT clause                                        */
+  int64_t offset, count;            /* LIMIT offset, count                                       */
+} nbg_order_request;
+int32_t nbg_order_by(nbg_engine* e, const nbg_rows* in, const nbg_order_request* req, nbg_rows** out);
+
 /* ---- FIND SHORTEST | ALL PATH (FindPathExecutor semantics) ----------------------------- */
 typedef struct {
   const int64_t* from;            /* de-duplicated by the callee (VerticesClause::prepare)    */
@@ -513,7 +571,9 @@ typedef struct {
 } nbg_kernel_stat;
 /* enable = 1 starts (and resets) timing of every launch; 2 times only the final-step /
  * shortest-path expansion kernels (two events per query: minimal perturbation of the timed
- * region); 0 stops timing. */
+ * region); 0 stops timing.  Mode 1 also times nbg_order_by's launches: k_ob_iota, k_ob_hist,
+ * k_ob_pick, k_ob_compact (the first-K selection), k_ob_image, ob_radix_sort, k_ob_gather,
+ * k_ob_copy (DESIGN.md "ORDER BY / LIMIT"). */
 /* ---- FIND PATH replica of a partitioned engine (replica.hip) ---------------------------------
  * A partitioned engine (num_gpus > 1) also builds, at nbg_finalize (collectively), a replica of
  * every rank's path CSRs (offsets, neighbour ids and vids, ranks; no property columns) when it fits

@@ -91,6 +91,11 @@ class nbg_group_request(C.Structure):
                 ("yield_aliases", P(C.c_char_p)), ("num_yields", i32)]
 
 
+class nbg_order_request(C.Structure):
+    _fields_ = [("input_names", P(C.c_char_p)), ("factor_names", P(C.c_char_p)), ("factor_desc", P(u8)),
+                ("num_factors", i32), ("has_limit", i32), ("offset", i64), ("count", i64)]
+
+
 # (name, restype, argtypes) for every symbol include/nbg.h declares
 SIGNATURES = [
     ("nbg_create", i32, [P(nbg_config), P(vp)]),
@@ -129,6 +134,7 @@ SIGNATURES = [
     ("nbg_rows_digest", i32, [vp, P(u64)]),
     ("nbg_rows_free", None, [vp]),
     ("nbg_group_by", i32, [vp, vp, P(nbg_group_request), P(vp)]),
+    ("nbg_order_by", i32, [vp, vp, P(nbg_order_request), P(vp)]),
     ("nbg_find_path", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_submit", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_wait", i32, [vp, P(vp)]),

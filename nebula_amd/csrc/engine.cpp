@@ -2368,6 +2368,120 @@ int32_t nbg_group_by(nbg_engine* h, const nbg_rows* in, const nbg_group_request*
   return NBG_OK;
 }
 
+// ============================================================================= ORDER BY / LIMIT
+// OrderByExecutor (src/graph/OrderByExecutor.cpp:94-155) and LimitExecutor
+// (src/graph/LimitExecutor.cpp:18-66) over a device-resident result; the kernels are in orderby.hip.
+int32_t nbg_order_by(nbg_engine* h, const nbg_rows* in, const nbg_order_request* rq, nbg_rows** out) {
+  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  // LimitExecutor::prepare (:18-28): before anything is executed, whatever the input holds
+  if (rq->has_limit && rq->offset < 0)
+    return E.fail(NBG_E_SYNTAX_ERROR, "skip `" + std::to_string(rq->offset) + "' is illegal");
+  if (rq->has_limit && rq->count < 0)
+    return E.fail(NBG_E_SYNTAX_ERROR, "count `" + std::to_string(rq->count) + "' is illegal");
+  if (in->eng != &E) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: the rows belong to another engine");
+  if (!in->on_device) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: the rows are host-only (not a device result)");
+  if (E.partitioned())
+    return E.fail(NBG_E_UNSUPPORTED, "ORDER BY on a partitioned engine (its rows live on several ranks)");
+  const int nf = rq->num_factors, nc = in->ncols;
+  if (nf < 0) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: negative factor count");
+  // the result carries the input's columns: one kind and one spelling of constants per column
+  std::unique_ptr<nbg_rows> res(gb_new_rows(E, nc));
+  res->derived = in->derived;
+  bool mixed = false, respelt = false;
+  for (int c = 0; c < nc; ++c) {
+    const int k = in->col_kind(c);
+    mixed = mixed || k < 0;
+    res->kinds[0][c] = k < 0 ? VK_INT : (VKind)k;
+    res->col_types[c] = c < (int)in->col_types.size() && in->col_types[c] ? in->col_types[c] : gb_natural_type(res->kinds[0][c]);
+    bool have = false;
+    for (auto& cs : in->const_str) {
+      if ((int)cs.size() <= c) continue;
+      respelt = respelt || (have && res->const_str[0][c] != cs[c]);
+      res->const_str[0][c] = cs[c];
+      have = true;
+    }
+  }
+  if (!in->count) {   // OrderByExecutor::beforeExecute (:137-139) and LimitExecutor: no rows, no check
+    *out = res.release();
+    return NBG_OK;
+  }
+  if (!rq->input_names || (nf > 0 && (!rq->factor_names || !rq->factor_desc)))
+    return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: null argument");
+  if (nf > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: more than NBG_MAX_YIELDS factors");
+  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: the rows have no columns");
+  std::vector<std::string> names;
+  for (int c = 0; c < nc; ++c) {
+    if (!rq->input_names[c]) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: null input column name");
+    names.emplace_back(rq->input_names[c]);
+  }
+  ObPlan plan;
+  plan.nf = nf;
+  plan.ncols = nc;
+  for (int f = 0; f < nf; ++f) {   // getFieldIndex: the first column of that name (:140-152)
+    if (!rq->factor_names[f]) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: null factor name");
+    auto it = std::find(names.begin(), names.end(), std::string(rq->factor_names[f]));
+    if (it == names.end())
+      return E.fail(NBG_E_EXECUTION_ERROR, std::string("Field (") + rq->factor_names[f] + ") not exist in input schema.");
+    plan.col[f] = (int8_t)(it - names.begin());
+    plan.desc[f] = rq->factor_desc[f] != 0;
+  }
+  // ---- device scope
+  if (in->misaligned || in->float_col)
+    return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (mixed) return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: a column mixes value kinds between OVER types");
+  if (respelt) return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: a string column spells different constants per OVER type");
+  for (int f = 0; f < nf; ++f) {
+    const int c = plan.col[f];
+    plan.dbl[f] = res->kinds[0][c] == VK_DOUBLE;
+    // dictionary codes order as their strings do (loader.cpp: the dictionary is sorted by
+    // std::string::operator<); a derived code or an out-of-dictionary constant does not
+    if (res->kinds[0][c] == VK_STRING && (!in->derived.empty() || !res->const_str[0][c].empty()))
+      return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: factor `" + names[c] + "' can hold strings outside the dictionary");
+  }
+  // ---- the window (LimitExecutor.cpp:30-66)
+  const uint64_t total = in->count;
+  plan.has_limit = rq->has_limit != 0;
+  plan.lo = 0;
+  plan.hi = total;
+  if (plan.has_limit) {
+    const uint64_t off = (uint64_t)rq->offset, cnt = (uint64_t)rq->count;
+    if (cnt == 0 || total <= off) {
+      *out = res.release();
+      return NBG_OK;
+    }
+    plan.lo = off;
+    plan.hi = cnt > total - off ? total : off + cnt;   // (off + cnt saturates)
+  }
+  if (plan.hi - plan.lo > 0xFFFFFFFFull)   // (a result segment's row count is 32 bits)
+    return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: a result of 2^32 rows or more");
+  // ---- the passes
+  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+  auto* m = const_cast<nbg_rows*>(in);
+  m->build_segs();
+  std::vector<std::pair<uint64_t, uint64_t>> segs;
+  for (auto& sg : m->segs)
+    if (sg.end > sg.begin) segs.emplace_back(sg.begin, sg.end - sg.begin);
+  Workspace* inw = in->owned_ws ? in->owned_ws : in->ws;
+  if (!inw) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: the rows have no device workspace");
+  Workspace* ow = nullptr;
+  std::string err;
+  if (int32_t rc = ws_order_by(inw, E.stream, segs, plan, &ow, &E.ob_prof, &err)) return E.fail(rc, err);
+  const uint64_t n = plan.hi - plan.lo;
+  res->ws = res->owned_ws = ow;
+  res->count = n;
+  nbg_rows::TypeBlocks tb;
+  tb.region = 0;
+  tb.blk_cap = n;
+  tb.counts.assign(1, (uint32_t)n);
+  res->blocks.push_back(std::move(tb));
+  for (int c = 0; c < nc; ++c) res->dcols.push_back(ws_row_col(ow, c));
+  *out = res.release();
+  return NBG_OK;
+}
+
 int32_t nbg_set_path_replica(nbg_engine* h, int32_t mode) {
   if (!h || mode < 0 || mode > 1) return NBG_E_INVALID_ARGUMENT;
   Engine& E = h->e;
@@ -2390,6 +2504,8 @@ int32_t nbg_profile(nbg_engine* h, int32_t enable) {
   if (!E.ws) return E.fail(NBG_E_STATE, "engine not finalized");
   const int mode = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
   ws_profile(E.ws, mode);
+  if (mode) E.ob_prof = ObProf{};   // (enabling resets the counters, as ws_profile does)
+  E.ob_prof.on = mode == 1;
   // the one-pair SHORTEST contexts (device-driven chains): their launches and algorithmic bytes
   for (Engine* P : {&E, E.rep.get()}) {   // (and the FIND PATH replica's)
     if (!P) continue;
@@ -2417,6 +2533,12 @@ int32_t nbg_profile_read(const nbg_engine* h, nbg_kernel_stat* out, int32_t cap)
     out[n].launches = (uint64_t)launches[k];
     out[n].total_ms = ms[k];
     out[n].algo_bytes = bytes[k];
+  }
+  for (int k = 0; k < OB_KINDS && n < cap; ++k, ++n) {   // nbg_order_by's kernels (orderby.hip)
+    out[n].name = kObKernelNames[k];
+    out[n].launches = E.ob_prof.launches[k];
+    out[n].total_ms = E.ob_prof.ms[k];
+    out[n].algo_bytes = E.ob_prof.bytes[k];
   }
   return n;
 }

@@ -59,6 +59,7 @@ struct Engine {
   uint64_t row_reserve = 0;             // result rows of the largest prepared GO statement (new
   int col_reserve = 0;                  // query workspaces are sized for it before their first query)
   int prof_mode = 0;
+  ObProf ob_prof;                       // nbg_order_by's kernels (nbg_profile mode 1)
   // pinned host blocks of fetched GO rows (nbg_rows_fetch), reused across queries
   std::mutex pinned_mu;
   std::vector<std::pair<size_t, void*>> pinned_free;

@@ -14,13 +14,13 @@
 #include <string>
 #include <vector>
 
+#include "ordimg.h"
 #include "ws.h"
 
 namespace nbg {
 
 namespace {
 
-constexpr uint64_t SIGN64 = 1ull << 63;
 constexpr int GB_ROUNDS = 8;   // groups a wave combines per 64 rows before its lanes go alone
 
 __device__ __forceinline__ uint64_t gb_mix64(uint64_t x) {
@@ -104,16 +104,6 @@ __device__ __forceinline__ void gb_apply(unsigned long long* p, uint8_t op, uint
   }
 }
 
-// order-preserving images for MAX / MIN: signed int64 and IEEE doubles onto unsigned order
-__device__ __forceinline__ uint64_t gb_ord(uint64_t v, uint8_t dbl) {
-  if (!dbl) return v ^ SIGN64;
-  return (v & SIGN64) ? ~v : (v | SIGN64);
-}
-__device__ __forceinline__ uint64_t gb_unord(uint64_t v, uint8_t dbl) {
-  if (!dbl) return v ^ SIGN64;
-  return (v & SIGN64) ? (v & ~SIGN64) : ~v;
-}
-
 __device__ __forceinline__ double gb_avg(uint64_t sum, bool dbl, uint64_t count) {
   const double s = dbl ? __longlong_as_double((long long)sum) : (double)(int64_t)sum;
   return __ddiv_rn(s, (double)count);
@@ -125,7 +115,7 @@ __device__ __forceinline__ uint64_t gb_value(const GbAcc& ac, int64_t* const* __
   const uint64_t v = (uint64_t)(ac.col >= 0 ? cols[ac.col][row] : ac.bits);
   switch (ac.op) {
     case GB_COUNT: return 1;
-    case GB_MAX: case GB_MIN: return gb_ord(v, ac.dbl);
+    case GB_MAX: case GB_MIN: return ord_image(v, ac.dbl);
     case GB_SQ: {
       const double x = ac.dbl ? __longlong_as_double((long long)v) : (double)(int64_t)v;
       const double d = __dsub_rn(x, gb_avg(gacc[(uint64_t)ac.ref * G + gid], ac.dbl, gacc[gid]));
@@ -298,8 +288,8 @@ __global__ void __launch_bounds__(BLOCK) k_gb_emit(const GbPlan* __restrict__ pl
       switch (ou.emit) {
         case GE_KEY: v = cols[ou.col][row]; break;
         case GE_CONST: v = ou.bits; break;
-        case GE_ORD_I: v = (int64_t)gb_unord(s, 0); break;
-        case GE_ORD_D: v = (int64_t)gb_unord(s, 1); break;
+        case GE_ORD_I: v = (int64_t)ord_unimage(s, 0); break;
+        case GE_ORD_D: v = (int64_t)ord_unimage(s, 1); break;
         case GE_AVG_I: v = __double_as_longlong(gb_avg(s, false, count)); break;
         case GE_AVG_D: v = __double_as_longlong(gb_avg(s, true, count)); break;
         case GE_STD:

@@ -729,6 +729,39 @@ constexpr uint64_t GB_LDS_BYTES = 16 * 1024;
 int32_t ws_group_by(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
                     const GbPlan& plan, Workspace** outw, uint64_t* groups, std::string* err);
 
+// ---- ORDER BY / LIMIT over device rows (orderby.hip; OrderByExecutor.cpp:94-155,
+// LimitExecutor.cpp:18-66).  The request planned to factor columns and a row window.
+struct ObPlan {
+  int nf = 0;                       // 0: LIMIT only (the input's own segment order)
+  int8_t col[MAX_YIELDS] = {};      // factor f's input column
+  uint8_t dbl[MAX_YIELDS] = {};     // ... is a DOUBLE column (IEEE order, -0.0 == 0.0)
+  uint8_t desc[MAX_YIELDS] = {};
+  bool has_limit = false;
+  uint64_t lo = 0, hi = 0;          // the result: rows [lo, hi) of the ordered input, lo < hi <= rows
+  int ncols = 0;
+};
+// With a LIMIT whose window ends at row K = hi, the first-K selection (radix select of the K-th
+// smallest first-factor image, then a compaction of the candidates) runs in front of the sort when
+// K * OB_SELECT_RATIO <= rows; else every row is sorted (DESIGN.md "ORDER BY / LIMIT").
+constexpr uint64_t OB_SELECT_RATIO = 8;
+constexpr uint64_t OB_CHUNK = 2048;   // rows a workgroup walks per chunk of a segment
+// nbg_profile_read's ORDER BY entries (kObKernelNames), timed while nbg_profile mode 1 is on
+enum ObKernel { OB_K_IOTA = 0, OB_K_HIST, OB_K_PICK, OB_K_COMPACT, OB_K_IMAGE, OB_K_SORT, OB_K_GATHER, OB_K_COPY,
+                OB_KINDS };
+extern const char* const kObKernelNames[OB_KINDS];
+struct ObProf {
+  bool on = false;
+  uint64_t launches[OB_KINDS] = {};
+  double ms[OB_KINDS] = {};
+  double bytes[OB_KINDS] = {};
+};
+// Orders the rows of `inw` listed by segs (first row, rows) and writes rows [lo, hi) of that order
+// into a fresh rows-only workspace on `stream` (*outw; ws_destroy releases it).  Synchronous;
+// every scratch allocation is released before it returns.  NBG_OK, NBG_E_OUT_OF_MEMORY or
+// NBG_E_DEVICE (*err names the failing call).
+int32_t ws_order_by(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
+                    const ObPlan& plan, Workspace** outw, ObProf* prof, std::string* err);
+
 // Query pipeline (all asynchronous on the workspace stream until ws_end_query):
 hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, const std::vector<TypeProgram>* progs,
                           uint64_t stmt_id);

@@ -401,6 +401,21 @@ class Engine:
         self._check(self.lib.nbg_group_by(self.h, rows.h, C.byref(req), C.byref(out)), "group_by")
         return DeviceRows(self, out)
 
+    def order_by(self, rows: DeviceRows, input_names, factors=(), limit=None) -> DeviceRows:
+        """nbg_order_by: ``| ORDER BY factors | LIMIT offset, count`` over a device-resident result,
+        either clause alone or both in one call.  ``input_names`` names ``rows``' columns,
+        ``factors`` is a list of ``(name, desc)`` and ``limit`` is None or ``(offset, count)``.  The
+        result is a new DeviceRows in result order; ``rows`` stays valid and unchanged."""
+        factors = list(factors)
+        names = (C.c_char_p * max(1, len(input_names)))(*[n.encode() for n in input_names])
+        fnames = (C.c_char_p * max(1, len(factors)))(*[f[0].encode() for f in factors])
+        desc = (C.c_uint8 * max(1, len(factors)))(*[1 if f[1] else 0 for f in factors])
+        off, cnt = (int(limit[0]), int(limit[1])) if limit is not None else (0, 0)
+        req = L.nbg_order_request(names, fnames, desc, len(factors), 0 if limit is None else 1, off, cnt)
+        out = C.c_void_p()
+        self._check(self.lib.nbg_order_by(self.h, rows.h, C.byref(req), C.byref(out)), "order_by")
+        return DeviceRows(self, out)
+
     def default_columns(self, etypes, over_all=False):
         """Edge types of a YIELD-less GO's `<edge>._dst` columns, in column order (OVER order;
         for OVER *, the response edge_schema's iteration order, GoExecutor.cpp:481-499)."""
