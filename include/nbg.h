@@ -349,7 +349,14 @@ void nbg_rows_free(nbg_rows* r);
  *   SUM    INT / VID / TIMESTAMP: int64, wrapping, the column's type; DOUBLE: double; else INT 0
  *   AVG    INT: double(sum) / count; DOUBLE: sum / count; BOOL / STRING: 0.0
  *   MAX / MIN  the column's own order and type: signed int64, IEEE doubles, false < true,
- *          dictionary strings by their sorted-dictionary codes
+ *          dictionary strings by their sorted-dictionary codes.  Doubles with NaNs: the
+ *          reference's answer depends on its row order (a NaN never replaces a value and
+ *          nothing replaces a leading NaN); here MAX / MIN reduce the IEEE total-order image
+ *          of the bits, as ORDER BY sorts them, whatever the row order: a negative NaN is
+ *          below -inf and a positive NaN above +inf, so the highest positive NaN of a group
+ *          is its MAX and the lowest negative NaN its MIN.  Over zeros of both signs, which
+ *          sign MAX / MIN report is unspecified (-0.0 == 0.0 in the reference's comparison)
+ *          (tests/test_gpu_values_groupby.py pins both)
  *   STD    INT / DOUBLE: sqrt(sum((x - avg)^2) / n), DOUBLE; else INT 0
  *   BIT_AND / BIT_OR / BIT_XOR  INT columns and int constants; else INT 0
  * Result column kinds follow those rules (generateOutputSchema, :355-391).  Row order is

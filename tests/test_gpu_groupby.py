@@ -15,7 +15,12 @@ BOOL column that gives the two-group shape (accumulators in LDS, worst contentio
 
 Two NBG_E_UNSUPPORTED cases of include/nbg.h have no test because no GO result reaches them: a
 column whose kind differs between OVER types (go_prepare coerces every OVER type's value to the
-column's type) and 2^32 groups."""
+column's type) and 2^32 groups.
+
+The cells these rows never hold (the int64 and double extremes, NaNs, negative VIDs, TIMESTAMPs,
+strings with bytes >= 0x80, values equal to an accumulator's identity) are the subject of
+tests/test_gpu_values_groupby.py; the LDS limit, the waves' group counts and probe chains that wrap
+are that of tests/test_gpu_rowtable_scale.py."""
 import math
 
 import numpy as np

@@ -17,7 +17,12 @@ window's edge cuts as a sub-multiset of the input's.
 
 One NBG_E_UNSUPPORTED case of include/nbg.h has no test because no GO result reaches it: a column
 whose kind differs between OVER types (go_prepare coerces every OVER type's value to the column's
-type); nor has the 2^32-row result."""
+type); nor has the 2^32-row result.
+
+The cells these rows never hold (the int64 and double extremes, ints whose middle bytes differ,
+NaNs, negative VIDs, TIMESTAMPs, strings with bytes >= 0x80) are the subject of
+tests/test_gpu_values_orderby.py; more chunks than workgroups and segments longer than a chunk are
+that of tests/test_gpu_rowtable_scale.py."""
 import ctypes as C
 
 import numpy as np
