@@ -264,6 +264,24 @@ int32_t nbg_go_prepare(nbg_engine* e, const nbg_go_request* req, nbg_go_stmt** o
 int32_t nbg_go_execute(nbg_go_stmt* stmt, const int64_t* starts, uint64_t num_starts, int32_t device,
                        nbg_rows** out);
 void nbg_go_stmt_free(nbg_go_stmt* stmt);
+/* The statement index.  A statement of at least two steps whose WHERE is `<edge column> <cmp>
+ * <integer constant>` (either side; < <= > >= == !=) and whose YIELDs are `_dst` or constants
+ * re-reads the WHERE column, and the `_dst` of the edges that fail, on every execution, while the
+ * snapshot never changes.  Once the statement's completed executions have together scanned
+ * NBG_STMT_INDEX_AFTER (default 0.25) times the OVER type's edge count in their final steps, the
+ * next nbg_go_execute / nbg_go_submit builds, for the statement's first OVER type, the type's
+ * adjacency restricted to the passing edges (4 bytes per vertex + 8 per passing edge of HBM, plus
+ * 4 bytes per edge of the type while it is built) and the statement's later final steps over that
+ * type copy rows from it (further OVER types keep the WHERE path).  Results,
+ * nbg_rows_edges_scanned and nbg_rows_step_stats are unchanged; queries already in flight finish
+ * as they were launched.  Not built: for nbg_go / nbg_go_device one-shots, on a partitioned
+ * engine, while max_edge_returned_per_vertex is below the type's largest degree, when the index
+ * with its build temporaries exceeds NBG_STMT_INDEX_MB (MiB; default: no limit) or half of the
+ * free device memory, or when an allocation fails (never a query error).  NBG_STMT_INDEX=0
+ * switches it off.  The three variables are read by nbg_go_prepare; NBG_STMT_INDEX_TRACE (any
+ * value) logs each build and its duration on stderr.  nbg_go_stmt_free releases the index.
+ * nbg_go_stmt_index_bytes: the HBM the statement's index holds (0: none). */
+uint64_t nbg_go_stmt_index_bytes(const nbg_go_stmt* stmt);
 
 /* Asynchronous execution (the way graphd runs concurrent queries): up to NBG_QUERY_SLOTS
  * (environment, default 6) queries of one engine in flight, each on its own workspace and HIP

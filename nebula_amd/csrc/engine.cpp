@@ -499,7 +499,16 @@ struct nbg_go_stmt {
   std::vector<std::string> in_xstr;
   uint32_t* d_xoff = nullptr;
   char* d_xbytes = nullptr;
+  // the filtered adjacency over the first OVER type (stmtidx.hip; nbg.h, nbg_go_prepare): built once
+  // the statement's completed executions have scanned idx_after x the type's edges in final steps
+  bool idx_on = false;               // made by nbg_go_prepare and not switched off
+  double idx_after = 0.25;           // NBG_STMT_INDEX_AFTER
+  uint64_t idx_budget = UINT64_MAX;  // NBG_STMT_INDEX_MB, in bytes
+  uint64_t final_scanned = 0;        // final-step edges of the completed executions
+  StmtIndex idx;
+  bool idx_tried = false;
   ~nbg_go_stmt() {
+    stmtidx_free(&idx);
     if (d_in_ids) (void)hipFree(d_in_ids);
     if (d_xoff) (void)hipFree(d_xoff);
     if (d_xbytes) (void)hipFree(d_xbytes);
@@ -891,6 +900,41 @@ struct GoPending {
   std::vector<uint64_t> region, blk_cap;
 };
 
+// Build the statement's filtered adjacency when it is due (under the engine mutex, before the
+// launch, on the engine's stream).  It is tried once: a skipped or failed build leaves the
+// statement on the WHERE path for good.  The first OVER type only: the final list of a later one
+// is a k_relist of the frontier, which drops the vertices whose edges all fail, and E_N counts them.
+template <typename ArgsFor>
+static void stmt_index_build(Engine& E, nbg_go_stmt* st, uint32_t cap, const ArgsFor& args_for) {
+  if (!st->idx_on || st->idx_tried || st->steps < 2 || E.partitioned() || st->deferred || st->over.empty()) return;
+  auto it = E.snap.types.find(st->over[0]);
+  if (it == E.snap.types.end()) return;
+  const DevEdgeType& dt = it->second;
+  if ((double)st->final_scanned < st->idx_after * (double)dt.num_edges) return;
+  st->idx_tried = true;
+  // a binding max_edge_returned_per_vertex clips the scanned degree before the WHERE runs: a cap
+  // over filtered degrees would change the results
+  if ((uint64_t)cap < (uint64_t)std::max(dt.max_degree, 0)) return;
+  const TypeProgram& prog = st->plist[0];
+  if (prog.where_const) return;   // (folded: nothing to filter, or a scan-only final step)
+  StmtIndexSpec sp{};
+  if (!ws_final_where(prog, args_for(dt), &sp)) return;
+  sp.nv = E.snap.nv;
+  sp.edges = dt.num_edges;
+  double ms = 0;
+  const bool ok = stmtidx_build(sp, st->idx_budget, E.stream, &st->idx, &ms);
+  if (getenv("NBG_STMT_INDEX_TRACE")) {
+    if (ok)
+      fprintf(stderr, "[stmt index] statement %llu type %d: built in %.3f ms after %llu final-step edges, %llu of %llu "
+                      "edges pass, %.1f MB\n", (unsigned long long)st->id, st->over[0], ms,
+              (unsigned long long)st->final_scanned, (unsigned long long)st->idx.rows,
+              (unsigned long long)dt.num_edges, (double)st->idx.bytes / 1e6);
+    else
+      fprintf(stderr, "[stmt index] statement %llu type %d: not built (memory budget or allocation), %.3f ms\n",
+              (unsigned long long)st->id, st->over[0], ms);
+  }
+}
+
 // Enqueue the whole query (every step, the final-step rows and the end-of-query copy) on the
 // workspace *wsp (its stream `stream`); no host synchronisation.  *wsp may be null (created here)
 // or hold an earlier device result's rows (handed to it first, ws_release).
@@ -1192,6 +1236,12 @@ static int32_t go_launch(Engine& E, const nbg_go_stmt* st, const int64_t* starts
     }
   }
   auto inl_of = [&](size_t i, uint32_t s) -> const InlineList* { return s == 1 && !inl.empty() ? &inl[i] : nullptr; };
+  stmt_index_build(E, const_cast<nbg_go_stmt*>(st), cap, args_for);
+  // the final step (and the list the step before it hands over) runs over the statement's
+  // filtered rows where it has them; queries already launched keep the arguments they have
+  auto index_of = [&](size_t i) -> const StmtIndex* {
+    return steps >= 2 && !part && i == 0 && st->idx.rp ? &st->idx : nullptr;
+  };
   hipError_t he = ws_begin_query(ws, f0.data(), f0.size(), &plist, st->id);
   // A tiny query — its walk bound (DevEdgeType::h_w2 / h_w3) keeps every step within one
   // workgroup — runs as one launch (ws_go_tiny); NBG_TINY=0 turns it off.
@@ -1238,6 +1288,7 @@ static int32_t go_launch(Engine& E, const nbg_go_stmt* st, const int64_t* starts
       auto it0 = E.snap.types.find(over[0]);
       if (it0 != E.snap.types.end()) {
         next0 = args_for(it0->second);
+        if (s + 1 == steps && index_of(0)) next0.row_ptr = index_of(0)->rp;
         np0 = &next0;
       }
     }
@@ -1252,6 +1303,11 @@ static int32_t go_launch(Engine& E, const nbg_go_stmt* st, const int64_t* starts
         he = ws_expand_mark(ws, a, n_bound, it->second.num_edges, (int)s, (int)i, inl_of(i, s), np0);
       } else if (deferred || (plist[i].where_const && !plist[i].where_const_val)) {
         he = ws_scan_only(ws, a, n_bound, (int)s, (int)i);
+      } else if (const StmtIndex* ix = index_of(i)) {
+        const uint32_t* const full = a.row_ptr;
+        a.row_ptr = ix->rp;
+        a.dst_vid = ix->dst;
+        he = ws_expand_final(ws, a, n_bound, ebound[i], (int)s, (int)i, plist[i], region[i], blk_cap[i], nullptr, full);
       } else {
         he = ws_expand_final(ws, a, n_bound, ebound[i], (int)s, (int)i, plist[i], region[i], blk_cap[i],
                              inl_of(i, s));
@@ -1406,6 +1462,7 @@ static int32_t go_collect(Engine& E, const nbg_go_stmt* st, GoPending* p, nbg_ro
     rows->step_edges.push_back(g_e[s]);
     rows->scanned += g_e[s];
   }
+  const_cast<nbg_go_stmt*>(st)->final_scanned += g_e[steps];
   const bool reached_final = g_n[steps] > 0;
   if (reached_final && deferred) { delete rows; return E.fail(deferred, st->deferred_msg); }
   if (reached_final && g_e[steps] > 0 && !st->dst_unknown.empty()) {
@@ -1912,6 +1969,15 @@ int32_t nbg_go_prepare(nbg_engine* h, const nbg_go_request* req, nbg_go_stmt** o
   std::lock_guard<std::mutex> lg(E.mu);
   const int32_t rc = go_prepare(E, req, out);
   if (rc || (*out)->steps < 2) return rc;
+  {   // the filtered-adjacency switches, read per statement (nbg.h)
+    nbg_go_stmt* st = *out;
+    const char* on = getenv("NBG_STMT_INDEX");
+    const char* after = getenv("NBG_STMT_INDEX_AFTER");
+    const char* mb = getenv("NBG_STMT_INDEX_MB");
+    st->idx_on = !(on && atoi(on) == 0);
+    if (after) st->idx_after = std::max(0.0, atof(after));
+    if (mb) st->idx_budget = strtoull(mb, nullptr, 10) << 20;
+  }
   // GoExecutor::prepare() validates once and execute() then only runs: size the row buffers of
   // the engine's workspace and of every query slot's now (growing a multi-GB buffer inside the
   // first execution cost that query ~0.2 s at RMAT-26).  A failure here is not an error: the
@@ -1935,6 +2001,12 @@ int32_t nbg_go_execute(nbg_go_stmt* st, const int64_t* starts, uint64_t num_star
 }
 
 void nbg_go_stmt_free(nbg_go_stmt* st) { delete st; }
+
+uint64_t nbg_go_stmt_index_bytes(const nbg_go_stmt* st) {
+  if (!st || !st->eng) return 0;
+  std::lock_guard<std::mutex> lg(st->eng->mu);
+  return st->idx.bytes;
+}
 
 int64_t nbg_rows_count(const nbg_rows* r) { return r ? (int64_t)r->count : -1; }
 int32_t nbg_rows_num_cols(const nbg_rows* r) { return r ? r->ncols : -1; }

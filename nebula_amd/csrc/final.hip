@@ -81,7 +81,7 @@ k_final_dst(FinalDstArgs a) {
   const unsigned long long packed = *a.acc;   // (list entries << 32 | edges)
   const uint64_t n = packed >> 32, total = packed & 0xFFFFFFFFull;
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    if (a.stat_e) *a.stat_e += total;
+    if (a.stat_e && !a.full_rp) *a.stat_e += total;
     if (a.stat_n) *a.stat_n = n;
   }
   if (threadIdx.x == 0) sBase = 0;
@@ -269,6 +269,15 @@ k_final_dst(FinalDstArgs a) {
     a1 = na1;
   }
   store_rows(pdv, ppm, preg);   // the wave's last tile
+  if (a.full_rp) {   // (uniform) E_N over the unfiltered rows: 64 frontier entries per wave and round
+    unsigned long long sum = 0;
+    for (uint64_t i = ((uint64_t)blockIdx.x * FW + w) * 64 + lane; i < n; i += g * 64) {
+      const uint32_t v = a.ids[i];
+      if (v != NO_ROW && (!a.visible || a.visible[v])) sum += a.full_rp[v + 1] - a.full_rp[v];
+    }
+    for (int o = 32; o; o >>= 1) sum += __shfl_down(sum, o, 64);
+    if (lane == 0 && sum) atomicAdd(a.stat_e, sum);
+  }
   __syncthreads();              // every wave of the workgroup has reserved its rows
   if (threadIdx.x == 0) a.blk_rows[blockIdx.x] = (uint32_t)sBase;
 }

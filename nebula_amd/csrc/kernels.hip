@@ -1971,6 +1971,9 @@ static double prof_bytes(const Workspace* w, const Prof::Rec& r, const QState& q
     case K_EXPAND_FINAL: {
       double rows = 0;
       for (unsigned b = 0; b < w->final_grid[r.tix]; ++b) rows += (double)w->h_blk_rows[(size_t)r.tix * EXPAND_GRID + b];
+      // over a statement's filtered adjacency (cols < 0): what the launch has to move — 8 per row
+      // read, 8 k per row written, 12 per list entry (edge offsets, row start, tile split)
+      if (r.cols < 0) return 8.0 * rows + 8.0 * rows * r.kout + 12.0 * (double)q.step_n[r.step];
       // SURVEY §8(d) B_GO final-step terms: 4 E_N neighbour ids + 8 E_N per WHERE/YIELD edge
       // property column + 8 k per emitted row
       return (double)q.e_st[r.step][r.tix] * (4.0 + 8.0 * r.cols) + 8.0 * rows * r.kout;
@@ -2585,10 +2588,36 @@ static bool lean_final() {
   return on;
 }
 
+// The final step runs final.hip's kernel with a WHERE column to read: the shape a statement's
+// filtered adjacency replaces.
+static bool final_where_shape(const FastProg& f, const ExpandArgs& a) {
+  bool dst_only = f.enabled != 0;
+  for (int y = 0; y < MAX_YIELDS; ++y) dst_only = dst_only && (f.ykind[y] == 0 || f.ykind[y] == 4);
+  return dst_only && lean_final() && f.dst_yield && a.dst_vid && f.has_where && f.wcol;
+}
+
+bool ws_final_where(const TypeProgram& prog, const ExpandArgs& a, StmtIndexSpec* sp) {
+  if (prog.yield_reg.size() > (size_t)MAX_YIELDS) return false;
+  const FastProg f = detect_fast(prog, a);
+  if (!final_where_shape(f, a)) return false;
+  sp->row_ptr = a.row_ptr;
+  sp->dst_vid = a.dst_vid;
+  sp->wcol = f.wcol;
+  sp->wbytes = f.wbytes;
+  sp->lo = f.lo;
+  sp->hi = f.hi;
+  sp->where_neg = f.where_neg;
+  return true;
+}
+
 hipError_t ws_expand_final(Workspace* w, const ExpandArgs& a0, uint64_t n_bound, uint64_t e_bound, int step, int tix,
-                           const TypeProgram& prog, uint64_t region_base, uint64_t blk_cap, const InlineList* il) {
+                           const TypeProgram& prog, uint64_t region_base, uint64_t blk_cap, const InlineList* il,
+                           const uint32_t* full_row_ptr) {
   if (step > MAX_STEPS || tix >= MAX_TYPES_Q) return hipErrorInvalidValue;
   const bool inl = inline_start_list(w, tix, il);
+  // a filtered adjacency needs the list to be the whole frontier (E_N counts vertices without
+  // passing edges too): the one the step before built, never a k_relist's, which drops them
+  if (full_row_ptr && (inl || tix != 0 || !w->seg_ready)) return hipErrorInvalidValue;
   const ListRef L = inl ? ListRef{nullptr, nullptr, &w->q->step_n[step], 0} : prepare_list(w, a0, n_bound, step, tix);
   ExpandArgs a = a0;
   a.frontier = L.ids;
@@ -2618,6 +2647,12 @@ hipError_t ws_expand_final(Workspace* w, const ExpandArgs& a0, uint64_t n_bound,
   a.str.arena_used = &w->q->arena_used;
   a.str.err_flag = &w->q->err;
   fp.fast = detect_fast(prog, a);
+  if (full_row_ptr) {   // a0's rows hold the passing edges only: no WHERE left to evaluate
+    if (!final_where_shape(fp.fast, a)) return hipErrorInvalidValue;
+    fp.fast.has_where = 0;
+    fp.fast.wcol = nullptr;
+    fp.fast.wbytes = 0;
+  }
   size_t lds = fp.fast.enabled ? 0 : (size_t)(prog.nregs > 0 ? prog.nregs : 1) * BLOCK * sizeof(int64_t);
   bool dst_only = fp.fast.enabled;   // YIELDs are _dst / constants: the deferred-store instantiation
   for (int y = 0; y < fp.nyields; ++y) dst_only = dst_only && (fp.fast.ykind[y] == 0 || fp.fast.ykind[y] == 4);
@@ -2662,6 +2697,13 @@ hipError_t ws_expand_final(Workspace* w, const ExpandArgs& a0, uint64_t n_bound,
     fa.blk_cap = blk_cap;
     fa.blk_rows = fp.blk_rows;
     fa.stat_e = e_st;
+    if (full_row_ptr) {
+      // the list is the whole frontier (the step before built it over the filtered rows, keeping
+      // vertices without edges): the kernel sums E_N over the unfiltered offsets itself
+      fa.full_rp = full_row_ptr;
+      fa.ids = L.ids;
+      fa.visible = a.visible;
+    }
     fa.stat_n = L.stat_n;
     fa.err_flag = &w->q->err;
     const bool one = fp.nyields == 1 && fa.const_mask == 0;
@@ -2683,7 +2725,7 @@ hipError_t ws_expand_final(Workspace* w, const ExpandArgs& a0, uint64_t n_bound,
     hipLaunchKernelGGL(k_expand<FINAL>, grid, dim3(BLOCK), lds, w->stream, a, L.acc, l_end, l_rs, w->flags,
                        fp, BfsParams{}, e_st, L.stat_n, NoInline{});
   }
-  prof_end(w, p, K_EXPAND_FINAL, step, tix, (double)edge_columns_read(prog), (double)fp.nyields);
+  prof_end(w, p, K_EXPAND_FINAL, step, tix, full_row_ptr ? -1.0 : (double)edge_columns_read(prog), (double)fp.nyields);
   w->final_grid[tix] = final_grid(n_bound, e_bound);
   return hipGetLastError();
 }

@@ -400,8 +400,36 @@ struct FinalDstArgs {
   unsigned long long* stat_e;
   unsigned long long* stat_n;
   unsigned long long* err_flag;    // QState::err (SPLIT_BAD)
+  // the rows are a statement's filtered adjacency (StmtIndex) and the list is the whole final
+  // frontier (non-null): stat_e receives the unfiltered degrees of ids[0..n) over full_rp, summed
+  // by the kernel's waves after their tiles, instead of the list's own (filtered) edge total
+  const uint32_t* full_rp;
+  const uint32_t* ids;
+  const uint8_t* visible;
 };
 hipError_t launch_final_dst(const FinalDstArgs& a, int wbytes, bool one, unsigned grid, hipStream_t s);
+
+// A prepared statement's filtered adjacency over one OVER type (stmtidx.hip): the type's rows
+// restricted to the edges passing the statement's WHERE `col <cmp> const`, original order kept.
+struct StmtIndexSpec {
+  const uint32_t* row_ptr;         // the type's CSR: nv + 1 offsets, edges _dst values
+  const int64_t* dst_vid;
+  uint64_t nv, edges;
+  const void* wcol;                // the WHERE column at its stored width (1/2/4/8 bytes)
+  int wbytes;
+  int64_t lo, hi;                  // pass = (lo <= w && w <= hi) != where_neg (FastProg)
+  int where_neg;
+};
+struct StmtIndex {
+  uint32_t* rp = nullptr;          // nv + 1 offsets into dst
+  int64_t* dst = nullptr;          // max(rows, 1) entries
+  uint64_t rows = 0;               // passing edges
+  uint64_t bytes = 0;              // device bytes held
+};
+// Build on stream s (synchronous).  False: no index (index + temporaries above budget_bytes or
+// half of the free device memory, or a failed allocation) and nothing is held.
+bool stmtidx_build(const StmtIndexSpec& sp, uint64_t budget_bytes, hipStream_t s, StmtIndex* out, double* ms);
+void stmtidx_free(StmtIndex* ix);
 
 // ----------------------------------------------------------------------------- FIND PATH state
 // Vertex labels are epoch-stamped so no per-query clearing is needed: label = epoch << LVL_BITS |
@@ -777,7 +805,14 @@ void ws_set_mark_claims(Workspace* w, bool claims);   // per query, before its f
 void ws_set_wake(Workspace* w, bool flag);   // the next end kernel wakes the host by its mapped flag
 // step N, per OVER type: scan + WHERE/YIELD + sharded row emission into [region_base, +NSHARD*shard_cap)
 hipError_t ws_expand_final(Workspace* w, const ExpandArgs& a, uint64_t n_bound, uint64_t e_bound, int step, int tix,
-                           const TypeProgram& prog, uint64_t region_base, uint64_t blk_cap, const InlineList* il = nullptr);
+                           const TypeProgram& prog, uint64_t region_base, uint64_t blk_cap, const InlineList* il = nullptr,
+                           const uint32_t* full_row_ptr = nullptr);
+// full_row_ptr (non-null; first OVER type only, whose list the step before built): a.row_ptr /
+// a.dst_vid are a statement's filtered adjacency (StmtIndex) and the WHERE is already applied; E_N
+// is summed from these unfiltered offsets over the whole frontier.
+// ws_final_where: the statement's final step over this type is the shape an index replaces
+// (WHERE `col <cmp> const`, YIELDs _dst / constants); fills every field of *sp but nv / edges.
+bool ws_final_where(const TypeProgram& prog, const ExpandArgs& a, StmtIndexSpec* sp);
 hipError_t ws_scan_only(Workspace* w, const ExpandArgs& a, uint64_t n_bound, int step, int tix);
 // roots (allocated on first use): *out written by MARKB, *in read (the same array on a single
 // engine; partitioned, out spans the global id space and in is the owner's local view, merged by

@@ -142,6 +142,10 @@ class GoStatement:
         finally:
             self.eng.lib.nbg_rows_free(out)
 
+    def index_bytes(self) -> int:
+        """HBM held by the statement's filtered adjacency (nbg_go_stmt_index_bytes; 0: none)."""
+        return int(self.eng.lib.nbg_go_stmt_index_bytes(self.h)) if self.h else 0
+
     def free(self):
         if self.h:
             self.eng.lib.nbg_go_stmt_free(self.h)
