@@ -79,6 +79,17 @@ extern "C" {
  *   table, or a per-OVER-type string constant for that column);
  *   a carried-over string column whose OVER types spell different constants outside the dictionary;
  *   more than NBG_MAX_YIELDS factors; a result of 2^32 rows or more.
+ * nbg_set_op (tests/test_gpu_setops.py holds one test per limit a GO result can reach; the
+ * mixed-kind column and the row counts are guards no test reaches):
+ *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
+ *   an input whose row schema re-reads its columns (a misaligned or FLOAT column);
+ *   a column whose value kind differs between OVER types (col_kind == -1);
+ *   a string column carrying a per-OVER-type constant outside the dictionary, on either side (its
+ *   code is private to its result, so the two inputs cannot be compared);
+ *   a column pair where exactly one side is STRING (the cast formats or parses strings);
+ *   a result of 2^32 rows or more; INTERSECT with a right input of 2^31 rows or more (a value's
+ *   multiplicity is a signed 32-bit counter).
+ *   The pass-through shortcuts have nbg_order_by's limits for the side passed on.
  * (A storage filter with a function call is E_INVALID_FILTER per part, as checkExp answers it,
  * QueryBaseProcessor.inl:172-290.)
  * Not limits: $- / $var input strings absent from the snapshot's dictionary, string functions
@@ -452,6 +463,76 @@ typedef struct {
 } nbg_order_request;
 int32_t nbg_order_by(nbg_engine* e, const nbg_rows* in, const nbg_order_request* req, nbg_rows** out);
 
+/* ---- UNION / INTERSECT / MINUS over two device-resident results (SetExecutor) ---------------
+ * `left UNION [ALL|DISTINCT] right`, `left INTERSECT right`, `left MINUS right` over rows in HBM
+ * (SetExecutor.cpp:98-383; grammar: parser.yy:1109-1141).  Inputs and output follow nbg_group_by's
+ * and nbg_order_by's contract: `left` and `right` are device-resident results of the same single
+ * engine (GO results, or outputs of nbg_group_by, nbg_order_by or nbg_set_op); left == right is
+ * allowed; both stay valid and unchanged.  `out` is an ordinary device-resident nbg_rows of one
+ * segment in a workspace of its own: every nbg_rows_* accessor works on it and it feeds
+ * nbg_group_by, nbg_order_by and nbg_set_op.  It carries no column names: the caller keeps the
+ * left operand's (SetExecutor.cpp:129).  The call runs under the engine lock on the engine's
+ * stream; its scratch (12 bytes per slot of a row table of twice the inserted rows, one flag byte
+ * per row, 24 bytes per chunk of 2,048 rows) is released before it returns.  A failed allocation
+ * is NBG_E_OUT_OF_MEMORY.
+ *
+ * Statuses, in this order:
+ *  1. NBG_E_INVALID_ARGUMENT: a null argument, `op` outside 1..3, rows of another engine, a
+ *     host-only result.
+ *  2. NBG_E_UNSUPPORTED: a partitioned engine.
+ *  3. NBG_E_EXECUTION_ERROR ("Field count not match."): different column counts, even when both
+ *     inputs are empty (:131-136, SetTest.ExecutionError).
+ *  4. The empty-input shortcuts, before any schema or cast check (:137-141, :163-174, :273-277,
+ *     :327-337): both empty: zero rows.  UNION with one side empty: the other side as it is, with
+ *     its own column types and not de-duplicated, even under DISTINCT.  INTERSECT with either side
+ *     empty, MINUS with the left empty: zero rows.  MINUS with the right empty: the left as it is.
+ *     "As it is" is exactly what nbg_order_by returns for that side with no factors and no LIMIT,
+ *     its NBG_E_UNSUPPORTED cases included.
+ *  5. Device scope: see "Device limits" (NBG_E_UNSUPPORTED; the caller then runs the reference's
+ *     loop over the fetched rows).  The two inputs' derived-string tables are merged on the host;
+ *     one derived code standing for two texts is NBG_E_EXECUTION_ERROR ("derived-string hash
+ *     collision").
+ *
+ * Implicit casts (checkSchema / doCasting, :219-262; InterimResult::castTo*, InterimResult.cpp:
+ * 292-538): column c's type is its col_type, or its kind's natural type when unset.  Where the two
+ * sides' types differ, every right cell is cast to the left's type, in all three operators and
+ * before any comparison; the result takes the left's kinds, types and string spelling.
+ *   INT / VID / TIMESTAMP among each other: the payload is unchanged.
+ *   DOUBLE to integer-like: truncation toward zero (NaN and |x| >= 2^63 are undefined in the
+ *   reference and unspecified here).  BOOL to integer-like: 0 / 1.
+ *   integer-like to DOUBLE: (double), round to nearest even.  BOOL to DOUBLE: 0.0 / 1.0.
+ *   integer-like to BOOL: != 0.  DOUBLE to BOOL: != 0.0 (NaN is true, -0.0 is false).
+ * A result row that came from the right holds the cast value.
+ *
+ * Row equality, after the cast and with the left's types: payload equality for integer-like, BOOL
+ * and string codes (dictionary codes and derived codes are engine-wide, so they compare across
+ * results); IEEE == for DOUBLE: -0.0 equals 0.0, and which sign a surviving row reports is
+ * unspecified.  A NaN cell equals nothing in INTERSECT and MINUS, as in the reference: such a left
+ * row never appears in an INTERSECT and always survives a MINUS.  In UNION DISTINCT the reference's
+ * sort comparator is undefined on NaN; here NaNs are equal by their bits, as in GROUP BY keys.
+ *
+ * Multiplicities, for a row value occurring cL times on the left and cR times on the right:
+ *   UNION ALL                cL + cR                (:208-210)
+ *   UNION / UNION DISTINCT   1                      (doDistinct, :265-269)
+ *   INTERSECT                min(cL, cR)            (:311-319: the reference moves the matched right
+ *                            row out of its vector; the moved-from row has no columns and matches
+ *                            nothing again, so every right row is used up by one left row)
+ *   MINUS                    cL if cR == 0, else 0  (:371-379)
+ * Row order: UNION ALL is the left's fetch order followed by the right's, so
+ * limit(union_all(a, b)) is exact like LIMIT-only nbg_order_by.  The other operators' order is
+ * unspecified (the reference's is the left's, or sorted for DISTINCT, but the left's own segment
+ * order is already not the reference's): pipe into nbg_order_by for an order.
+ * Single engine only: merging the ranks' rows of a partitioned engine is a later change. */
+#define NBG_SET_UNION     1
+#define NBG_SET_INTERSECT 2
+#define NBG_SET_MINUS     3
+typedef struct {
+  int32_t op;        /* NBG_SET_* */
+  int32_t distinct;  /* UNION only: 0 = UNION ALL, else UNION / UNION DISTINCT; ignored otherwise */
+} nbg_set_request;
+int32_t nbg_set_op(nbg_engine* e, const nbg_rows* left, const nbg_rows* right, const nbg_set_request* req,
+                   nbg_rows** out);
+
 /* ---- FIND SHORTEST | ALL PATH (FindPathExecutor semantics) ----------------------------- */
 typedef struct {
   const int64_t* from;            /* de-duplicated by the callee (VerticesClause::prepare)    */
@@ -598,7 +679,8 @@ typedef struct {
  * shortest-path expansion kernels (two events per query: minimal perturbation of the timed
  * region); 0 stops timing.  Mode 1 also times nbg_order_by's launches: k_ob_iota, k_ob_hist,
  * k_ob_pick, k_ob_compact (the first-K selection), k_ob_image, ob_radix_sort, k_ob_gather,
- * k_ob_copy (DESIGN.md "ORDER BY / LIMIT"). */
+ * k_ob_copy (DESIGN.md "ORDER BY / LIMIT"), and nbg_set_op's: k_so_insert, k_so_probe, k_so_emit,
+ * k_so_copy (DESIGN.md "Set operations over device rows"). */
 /* ---- FIND PATH replica of a partitioned engine (replica.hip) ---------------------------------
  * A partitioned engine (num_gpus > 1) also builds, at nbg_finalize (collectively), a replica of
  * every rank's path CSRs (offsets, neighbour ids and vids, ranks; no property columns) when it fits

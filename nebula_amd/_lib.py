@@ -96,6 +96,14 @@ class nbg_order_request(C.Structure):
                 ("num_factors", i32), ("has_limit", i32), ("offset", i64), ("count", i64)]
 
 
+class nbg_set_request(C.Structure):
+    _fields_ = [("op", i32), ("distinct", i32)]
+
+
+SET_UNION, SET_INTERSECT, SET_MINUS = 1, 2, 3
+SET_BY_NAME = {"UNION": SET_UNION, "INTERSECT": SET_INTERSECT, "MINUS": SET_MINUS}
+
+
 # (name, restype, argtypes) for every symbol include/nbg.h declares
 SIGNATURES = [
     ("nbg_create", i32, [P(nbg_config), P(vp)]),
@@ -136,6 +144,7 @@ SIGNATURES = [
     ("nbg_rows_free", None, [vp]),
     ("nbg_group_by", i32, [vp, vp, P(nbg_group_request), P(vp)]),
     ("nbg_order_by", i32, [vp, vp, P(nbg_order_request), P(vp)]),
+    ("nbg_set_op", i32, [vp, vp, vp, P(nbg_set_request), P(vp)]),
     ("nbg_find_path", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_submit", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_wait", i32, [vp, P(vp)]),

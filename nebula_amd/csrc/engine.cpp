@@ -2443,11 +2443,8 @@ int32_t nbg_group_by(nbg_engine* h, const nbg_rows* in, const nbg_group_request*
 // ============================================================================= ORDER BY / LIMIT
 // OrderByExecutor (src/graph/OrderByExecutor.cpp:94-155) and LimitExecutor
 // (src/graph/LimitExecutor.cpp:18-66) over a device-resident result; the kernels are in orderby.hip.
-int32_t nbg_order_by(nbg_engine* h, const nbg_rows* in, const nbg_order_request* rq, nbg_rows** out) {
-  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
-  *out = nullptr;
-  Engine& E = h->e;
-  std::lock_guard<std::mutex> lg(E.mu);
+// (under the engine lock; nbg_set_op's pass-through shortcuts are this with no factors and no LIMIT)
+static int32_t order_by_locked(Engine& E, const nbg_rows* in, const nbg_order_request* rq, nbg_rows** out) {
   // LimitExecutor::prepare (:18-28): before anything is executed, whatever the input holds
   if (rq->has_limit && rq->offset < 0)
     return E.fail(NBG_E_SYNTAX_ERROR, "skip `" + std::to_string(rq->offset) + "' is illegal");
@@ -2554,6 +2551,123 @@ int32_t nbg_order_by(nbg_engine* h, const nbg_rows* in, const nbg_order_request*
   return NBG_OK;
 }
 
+int32_t nbg_order_by(nbg_engine* h, const nbg_rows* in, const nbg_order_request* rq, nbg_rows** out) {
+  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  return order_by_locked(E, in, rq, out);
+}
+
+// ============================================================================= UNION / INTERSECT / MINUS
+// SetExecutor (src/graph/SetExecutor.cpp:98-383) over two device-resident results; the kernels
+// are in setops.hip.
+int32_t nbg_set_op(nbg_engine* h, const nbg_rows* left, const nbg_rows* right, const nbg_set_request* rq,
+                   nbg_rows** out) {
+  if (!h || !left || !right || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  if (rq->op < NBG_SET_UNION || rq->op > NBG_SET_MINUS) return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: unknown operator");
+  if (left->eng != &E || right->eng != &E)
+    return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: the rows belong to another engine");
+  if (!left->on_device || !right->on_device)
+    return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: the rows are host-only (not a device result)");
+  if (E.partitioned())
+    return E.fail(NBG_E_UNSUPPORTED, "set operation on a partitioned engine (its rows live on several ranks)");
+  const int nc = left->ncols;
+  if (nc != right->ncols) return E.fail(NBG_E_EXECUTION_ERROR, "Field count not match.");
+  // ---- the empty-input shortcuts (SetExecutor.cpp:137-141, :163-174, :273-277, :327-337): before
+  // any schema check; a side passed on is what ORDER BY without factors and LIMIT makes of it
+  const bool uni = rq->op == NBG_SET_UNION;
+  auto as_it_is = [&](const nbg_rows* side) {
+    std::vector<const char*> names((size_t)std::max(side->ncols, 1), "");
+    nbg_order_request pass{};
+    pass.input_names = names.data();
+    return order_by_locked(E, side, &pass, out);
+  };
+  if (!left->count || !right->count) {
+    if (uni && right->count) return as_it_is(right);
+    if ((uni || rq->op == NBG_SET_MINUS) && left->count) return as_it_is(left);
+    *out = gb_new_rows(E, nc);   // (both empty, INTERSECT with an empty side, MINUS from nothing)
+    return NBG_OK;
+  }
+  // ---- device scope, and the casts (checkSchema / doCasting, :219-262)
+  if (left->misaligned || left->float_col || right->misaligned || right->float_col)
+    return E.fail(NBG_E_UNSUPPORTED, "set operation: an input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: the rows have no columns");
+  std::unique_ptr<nbg_rows> res(gb_new_rows(E, nc));
+  SoPlan plan;
+  plan.op = rq->op;
+  plan.distinct = uni && rq->distinct;
+  plan.ncols = nc;
+  auto type_of = [](const nbg_rows* r, int c, VKind k) {
+    return c < (int)r->col_types.size() && r->col_types[c] ? r->col_types[c] : gb_natural_type(k);
+  };
+  auto int_like = [](int32_t t) { return t == NBG_T_INT || t == NBG_T_VID || t == NBG_T_TIMESTAMP; };
+  for (int c = 0; c < nc; ++c) {
+    const int lk = left->col_kind(c), rk = right->col_kind(c);
+    if (lk < 0 || rk < 0) return E.fail(NBG_E_UNSUPPORTED, "set operation: a column mixes value kinds between OVER types");
+    const int32_t lt = type_of(left, c, (VKind)lk), rt = type_of(right, c, (VKind)rk);
+    if ((lt == NBG_T_STRING) != (rt == NBG_T_STRING))
+      return E.fail(NBG_E_UNSUPPORTED, "set operation: column " + std::to_string(c) + " casts to or from STRING");
+    if (lt == NBG_T_STRING) {
+      // a constant outside the dictionary has a code private to its result: nothing to compare it by
+      for (const nbg_rows* r : {left, right})
+        for (auto& cs : r->const_str)
+          if ((int)cs.size() > c && !cs[c].empty())
+            return E.fail(NBG_E_UNSUPPORTED, "set operation: string column " + std::to_string(c) +
+                                                 " carries a constant outside the dictionary");
+    }
+    res->kinds[0][c] = (VKind)lk;
+    res->col_types[c] = lt;
+    plan.dbl[c] = lt == NBG_T_DOUBLE;
+    uint8_t cast = SO_KEEP;
+    if (lt != rt) {
+      if (int_like(lt)) cast = rt == NBG_T_DOUBLE ? SO_D2I : rt == NBG_T_BOOL ? SO_B2I : SO_KEEP;
+      else if (lt == NBG_T_DOUBLE) cast = rt == NBG_T_BOOL ? SO_B2D : SO_I2D;
+      else if (lt == NBG_T_BOOL) cast = rt == NBG_T_DOUBLE ? SO_D2B : SO_I2B;
+    }
+    plan.cast[c] = cast;
+  }
+  // the derived strings of both inputs (their codes are content hashes, the same in every result)
+  res->derived = left->derived;
+  for (auto& kv : right->derived) {
+    auto ins = res->derived.emplace(kv.first, kv.second);
+    if (!ins.second && ins.first->second != kv.second) return E.fail(NBG_E_EXECUTION_ERROR, "derived-string hash collision");
+  }
+  // ---- the passes
+  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+  std::vector<std::pair<uint64_t, uint64_t>> segs[2];
+  Workspace* inw[2] = {nullptr, nullptr};
+  const nbg_rows* sides[2] = {left, right};
+  for (int s = 0; s < 2; ++s) {
+    auto* m = const_cast<nbg_rows*>(sides[s]);
+    m->build_segs();
+    for (auto& sg : m->segs)
+      if (sg.end > sg.begin) segs[s].emplace_back(sg.begin, sg.end - sg.begin);
+    inw[s] = m->owned_ws ? m->owned_ws : m->ws;
+    if (!inw[s]) return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: the rows have no device workspace");
+  }
+  Workspace* ow = nullptr;
+  uint64_t n = 0;
+  std::string err;
+  if (int32_t rc = ws_set_op(inw[0], inw[1], E.stream, segs[0], segs[1], plan, &ow, &n, &E.so_prof, &err))
+    return E.fail(rc, err);
+  if (ow) {
+    res->ws = res->owned_ws = ow;
+    res->count = n;
+    nbg_rows::TypeBlocks tb;
+    tb.region = 0;
+    tb.blk_cap = n;
+    tb.counts.assign(1, (uint32_t)n);
+    res->blocks.push_back(std::move(tb));
+    for (int c = 0; c < nc; ++c) res->dcols.push_back(ws_row_col(ow, c));
+  }
+  *out = res.release();
+  return NBG_OK;
+}
+
 int32_t nbg_set_path_replica(nbg_engine* h, int32_t mode) {
   if (!h || mode < 0 || mode > 1) return NBG_E_INVALID_ARGUMENT;
   Engine& E = h->e;
@@ -2578,6 +2692,8 @@ int32_t nbg_profile(nbg_engine* h, int32_t enable) {
   ws_profile(E.ws, mode);
   if (mode) E.ob_prof = ObProf{};   // (enabling resets the counters, as ws_profile does)
   E.ob_prof.on = mode == 1;
+  if (mode) E.so_prof = SoProf{};
+  E.so_prof.on = mode == 1;
   // the one-pair SHORTEST contexts (device-driven chains): their launches and algorithmic bytes
   for (Engine* P : {&E, E.rep.get()}) {   // (and the FIND PATH replica's)
     if (!P) continue;
@@ -2611,6 +2727,12 @@ int32_t nbg_profile_read(const nbg_engine* h, nbg_kernel_stat* out, int32_t cap)
     out[n].launches = E.ob_prof.launches[k];
     out[n].total_ms = E.ob_prof.ms[k];
     out[n].algo_bytes = E.ob_prof.bytes[k];
+  }
+  for (int k = 0; k < SO_KINDS && n < cap; ++k, ++n) {   // nbg_set_op's kernels (setops.hip)
+    out[n].name = kSoKernelNames[k];
+    out[n].launches = E.so_prof.launches[k];
+    out[n].total_ms = E.so_prof.ms[k];
+    out[n].algo_bytes = E.so_prof.bytes[k];
   }
   return n;
 }

@@ -60,6 +60,7 @@ struct Engine {
   int col_reserve = 0;                  // query workspaces are sized for it before their first query)
   int prof_mode = 0;
   ObProf ob_prof;                       // nbg_order_by's kernels (nbg_profile mode 1)
+  SoProf so_prof;                       // nbg_set_op's kernels
   // pinned host blocks of fetched GO rows (nbg_rows_fetch), reused across queries
   std::mutex pinned_mu;
   std::vector<std::pair<size_t, void*>> pinned_free;

@@ -790,6 +790,44 @@ struct ObProf {
 int32_t ws_order_by(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
                     const ObPlan& plan, Workspace** outw, ObProf* prof, std::string* err);
 
+// ---- UNION / INTERSECT / MINUS over device rows (setops.hip; SetExecutor.cpp:98-383).  The
+// request planned per column: how two cells compare and what casts a right cell to the left's type.
+enum SoCast : uint8_t {
+  SO_KEEP = 0,   // same type, or INT / VID / TIMESTAMP among each other
+  SO_D2I,        // DOUBLE -> integer-like: truncation toward zero
+  SO_B2I,        // BOOL -> integer-like: 0 / 1
+  SO_I2D,        // integer-like -> DOUBLE: (double), round to nearest even
+  SO_B2D,        // BOOL -> DOUBLE: 0.0 / 1.0
+  SO_I2B,        // integer-like -> BOOL: != 0
+  SO_D2B,        // DOUBLE -> BOOL: != 0.0 (NaN is true, -0.0 is false)
+};
+struct SoPlan {
+  int32_t op = 0;                   // NBG_SET_*
+  int32_t distinct = 0;             // UNION: the result keeps one row per value
+  int32_t ncols = 0;
+  uint8_t dbl[MAX_YIELDS] = {};     // the column compares as DOUBLE (the left's type): -0.0 == 0.0
+  uint8_t cast[MAX_YIELDS] = {};    // SoCast of the right side's cells
+};
+constexpr uint64_t SO_MIN_SLOTS = 1024;   // the row table: 2 x inserted rows, a power of two, at least this
+// nbg_profile_read's set-operation entries (kSoKernelNames), timed while nbg_profile mode 1 is on
+enum SoKernel { SO_K_INSERT = 0, SO_K_PROBE, SO_K_EMIT, SO_K_COPY, SO_KINDS };
+extern const char* const kSoKernelNames[SO_KINDS];
+struct SoProf {
+  bool on = false;
+  uint64_t launches[SO_KINDS] = {};
+  double ms[SO_KINDS] = {};
+  double bytes[SO_KINDS] = {};
+};
+// Combines the rows of `lw` listed by lsegs with those of `rw` listed by rsegs (first row, rows)
+// into a fresh rows-only workspace on `stream` (*outw; nullptr when the result has no rows) of
+// *rows rows.  Synchronous; every scratch allocation is released before it returns.  NBG_OK,
+// NBG_E_OUT_OF_MEMORY, NBG_E_UNSUPPORTED (a result of 2^32 rows or more) or NBG_E_DEVICE (*err
+// names the failing call).
+int32_t ws_set_op(Workspace* lw, Workspace* rw, hipStream_t stream,
+                  const std::vector<std::pair<uint64_t, uint64_t>>& lsegs,
+                  const std::vector<std::pair<uint64_t, uint64_t>>& rsegs, const SoPlan& plan, Workspace** outw,
+                  uint64_t* rows, SoProf* prof, std::string* err);
+
 // Query pipeline (all asynchronous on the workspace stream until ws_end_query):
 hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, const std::vector<TypeProgram>* progs,
                           uint64_t stmt_id);

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "ordimg.h"
+#include "stage.h"
 #include "ws.h"
 
 namespace nbg {
@@ -37,7 +38,7 @@ const char* const kObKernelNames[OB_KINDS] = {"k_ob_iota", "k_ob_hist", "k_ob_pi
 namespace {
 
 constexpr uint32_t OB_DBL = 1u, OB_DESC = 2u;
-constexpr unsigned OB_GRID = 2048;   // 8 workgroups per CU; the chunks beyond are grid-strided
+constexpr unsigned OB_GRID = STAGE_GRID;
 
 // a factor cell's sort image
 __device__ __forceinline__ uint64_t ob_image(int64_t v, uint32_t flags) {
@@ -47,9 +48,7 @@ __device__ __forceinline__ uint64_t ob_image(int64_t v, uint32_t flags) {
   return (flags & OB_DESC) ? ~u : u;
 }
 
-__device__ __forceinline__ uint32_t ob_lane_rank(unsigned long long bal) {   // set bits below this lane
-  return __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-}
+__device__ __forceinline__ uint32_t ob_lane_rank(unsigned long long bal) { return lane_rank(bal); }
 
 // the selection's state: one copy in HBM, advanced by k_ob_pick between the histogram passes
 struct ObSel {
@@ -201,72 +200,11 @@ __global__ void __launch_bounds__(BLOCK) k_ob_copy(const uint64_t* __restrict__ 
   }
 }
 
-// scratch of one call, released when it returns
-struct ObScratch {
-  std::vector<void*> ptrs;
-  hipError_t alloc(void** p, size_t bytes) {
-    *p = nullptr;
-    const hipError_t e = hipMalloc(p, bytes ? bytes : 8);
-    if (e == hipSuccess) ptrs.push_back(*p);
-    else (void)hipGetLastError();
-    return e;
-  }
-  ~ObScratch() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-};
+using ObScratch = StageScratch;
+using ObTimer = StageTimer<ObProf>;
 
-// an event pair around each launch while nbg_profile is on, resolved after the call's last wait
-struct ObTimer {
-  ObProf* prof;
-  hipStream_t stream;
-  struct Rec { int kind; hipEvent_t a, b; double bytes; };
-  std::vector<Rec> recs;
-  hipEvent_t open = nullptr;
-  bool on() const { return prof && prof->on; }
-  void begin() {
-    if (!on()) return;
-    if (hipEventCreate(&open) != hipSuccess) { open = nullptr; return; }
-    (void)hipEventRecord(open, stream);
-  }
-  void end(int kind, double bytes) {
-    if (!open) return;
-    hipEvent_t b = nullptr;
-    if (hipEventCreate(&b) == hipSuccess) {
-      (void)hipEventRecord(b, stream);
-      recs.push_back({kind, open, b, bytes});
-    } else {
-      (void)hipEventDestroy(open);
-    }
-    open = nullptr;
-  }
-  ~ObTimer() {
-    for (auto& r : recs) {
-      float ms = 0.f;
-      if (hipEventSynchronize(r.b) == hipSuccess && hipEventElapsedTime(&ms, r.a, r.b) == hipSuccess) {
-        prof->launches[r.kind]++;
-        prof->ms[r.kind] += ms;
-        prof->bytes[r.kind] += r.bytes;
-      }
-      (void)hipEventDestroy(r.a);
-      (void)hipEventDestroy(r.b);
-    }
-    if (open) (void)hipEventDestroy(open);
-  }
-};
-
-// the rows of `segs` inside logical rows [lo, hi), cut into chunks of at most OB_CHUNK rows; a
-// chunk's third word is its first row's logical index minus lo
 std::vector<uint64_t> ob_chunks(const std::vector<std::pair<uint64_t, uint64_t>>& segs, uint64_t lo, uint64_t hi) {
-  std::vector<uint64_t> out;
-  uint64_t at = 0;
-  for (auto& sg : segs) {
-    const uint64_t s0 = std::max(at, lo), s1 = std::min(at + sg.second, hi);
-    for (uint64_t p = s0; p < s1; p += OB_CHUNK)
-      out.insert(out.end(), {sg.first + (p - at), std::min<uint64_t>(OB_CHUNK, s1 - p), p - lo});
-    at += sg.second;
-  }
-  return out;
+  return stage_chunks(segs, lo, hi);
 }
 
 unsigned ob_flat_grid(uint64_t n) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(cdiv(n, BLOCK), 1), OB_GRID); }

@@ -278,8 +278,8 @@ class Engine:
         self._check(self.lib.nbg_profile(self.h, int(enable)), "profile")
 
     def profile_read(self):
-        arr = (L.nbg_kernel_stat * 32)()
-        n = self.lib.nbg_profile_read(self.h, arr, 32)
+        arr = (L.nbg_kernel_stat * 64)()
+        n = self.lib.nbg_profile_read(self.h, arr, 64)
         return {arr[i].name.decode(): {"launches": arr[i].launches, "ms": arr[i].total_ms,
                                        "algo_bytes": arr[i].algo_bytes} for i in range(n)}
 
@@ -418,6 +418,17 @@ class Engine:
         req = L.nbg_order_request(names, fnames, desc, len(factors), 0 if limit is None else 1, off, cnt)
         out = C.c_void_p()
         self._check(self.lib.nbg_order_by(self.h, rows.h, C.byref(req), C.byref(out)), "order_by")
+        return DeviceRows(self, out)
+
+    def set_op(self, left: DeviceRows, right: DeviceRows, op, distinct=False) -> DeviceRows:
+        """nbg_set_op: ``left UNION [ALL|DISTINCT] right``, ``left INTERSECT right`` or ``left MINUS
+        right`` over two device-resident results.  ``op`` is an NBG_SET_* value or its name
+        ("UNION" / "INTERSECT" / "MINUS"); ``distinct`` matters for UNION only (False: UNION ALL).
+        The result is a new DeviceRows with the left's column types; both inputs stay valid and
+        unchanged."""
+        req = L.nbg_set_request(L.SET_BY_NAME[op.upper()] if isinstance(op, str) else int(op), 1 if distinct else 0)
+        out = C.c_void_p()
+        self._check(self.lib.nbg_set_op(self.h, left.h, right.h, C.byref(req), C.byref(out)), "set_op")
         return DeviceRows(self, out)
 
     def default_columns(self, etypes, over_all=False):
