@@ -21,6 +21,8 @@
  *       AggregateFunction.h)
  *   nbg_order_by               ≙ OrderByExecutor + LimitExecutor (src/graph/OrderByExecutor.cpp:14-155,
  *       src/graph/LimitExecutor.cpp:18-66)
+ *   nbg_set_op                 ≙ SetExecutor (src/graph/SetExecutor.cpp:98-383)
+ *   nbg_yield                  ≙ YieldExecutor over piped rows (src/graph/YieldExecutor.cpp:178-282)
  *   nbg_get_neighbors          ≙ StorageServiceHandler::future_getBound → QueryBoundProcessor
  *       (src/storage/StorageServiceHandler.cpp:33-40, src/storage/QueryBoundProcessor.cpp:16-220)
  */
@@ -90,6 +92,18 @@ extern "C" {
  *   a result of 2^32 rows or more; INTERSECT with a right input of 2^31 rows or more (a value's
  *   multiplicity is a signed 32-bit counter).
  *   The pass-through shortcuts have nbg_order_by's limits for the side passed on.
+ * nbg_yield (tests/test_gpu_yield.py holds one test per limit a GO result can reach; the mixed-kind
+ * column, the differently spelt constants and the row count are guards no test reaches):
+ *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
+ *   any aggregate function (yield_funs[i] != NBG_AGG_NONE): whole-input aggregates without GROUP BY;
+ *   a WHERE or YIELD that builds a string (concatenation, a cast to string, string functions);
+ *   any use other than a bare pass-through column of a string column that can hold strings outside
+ *   the dictionary (a non-empty derived table, or a per-OVER-type constant outside the dictionary);
+ *   a passed-through string column whose OVER types spell different constants outside the dictionary;
+ *   a referenced column whose value kind differs between OVER types (col_kind == -1);
+ *   an input whose row schema re-reads its columns (a misaligned or FLOAT column);
+ *   more than NBG_MAX_YIELDS columns after `$-.*' expansion; a program over 256 instructions or
+ *   over the interpreter's register limit; an input of 2^32 rows or more.
  * (A storage filter with a function call is E_INVALID_FILTER per part, as checkExp answers it,
  * QueryBaseProcessor.inl:172-290.)
  * Not limits: $- / $var input strings absent from the snapshot's dictionary, string functions
@@ -533,9 +547,76 @@ typedef struct {
 int32_t nbg_set_op(nbg_engine* e, const nbg_rows* left, const nbg_rows* right, const nbg_set_request* req,
                    nbg_rows** out);
 
+/* ---- piped YIELD ... WHERE over a device-resident result (YieldExecutor) ---------------------
+ * `| YIELD $-.d AS id, $-.w * 2 AS w2 WHERE $-.w > 50` over rows in HBM
+ * (YieldExecutor::executeInputs, YieldExecutor.cpp:178-282; grammar: parser.yy:707-713; a YIELD
+ * sentence has no DISTINCT).  Input and output follow nbg_order_by's contract: `in` is a
+ * device-resident result of the same single engine (a GO result, or the output of nbg_group_by,
+ * nbg_order_by, nbg_set_op or nbg_yield itself); it stays valid and unchanged.  A host-only result,
+ * or one of another engine, is NBG_E_INVALID_ARGUMENT.  `out` is an ordinary device-resident
+ * nbg_rows of one segment in a workspace of its own: every nbg_rows_* accessor works on it and it
+ * feeds nbg_group_by, nbg_order_by, nbg_set_op and nbg_yield.  It carries no column names (the
+ * caller keeps the YIELD aliases).  The call runs under the engine lock on the engine's stream; its
+ * scratch (one flag byte per row, 32 bytes per chunk of 2,048 rows, the compiled program) is
+ * released before it returns.  A failed allocation is NBG_E_OUT_OF_MEMORY.
+ *
+ * Row order: the input's fetch order (segment order) with the failing rows removed, as the
+ * reference delivers it.  So `ORDER BY | YIELD | LIMIT` and `YIELD | LIMIT` are exact.
+ *
+ * Statuses, in this order:
+ *  1. NBG_E_INVALID_ARGUMENT: a null argument, num_yields < 1, a host-only or foreign `in`,
+ *     expression bytes that do not decode (nbg_go's rules, the cast wire extension included).
+ *  2. NBG_E_UNSUPPORTED: a partitioned engine.
+ *  3. NBG_E_SYNTAX_ERROR: any `$^', `$$' or edge-property node in WHERE or a YIELD (syntaxCheck,
+ *     :116-122; YieldTest.error); some yield_funs[i] != NBG_AGG_NONE together with a column that is
+ *     a bare `$-.x' / `$var.x' without a function (checkAggFun, :33-58; YieldTest.AggCall).
+ *  4. NBG_E_EXECUTION_ERROR: both `$-' and `$var' referenced, or more than one variable name
+ *     (:124-135).
+ *  5. Zero input rows: NBG_OK and a zero-row result with one column per YIELD after `$-.*'
+ *     expansion.  Whether unknown column names are diagnosed here is unspecified (the reference
+ *     dereferences a null schema).
+ *  6. A `$-.name' / `$var.name' absent from input_names: NBG_E_EXECUTION_ERROR ("column `x' not
+ *     exist in input.", :298-316; YieldTest.error).  With duplicate names the first match wins.
+ *  7. Device scope: see "Device limits" (NBG_E_UNSUPPORTED; the caller then runs the reference's
+ *     loop over the fetched rows).
+ *  8. Evaluation (NBG_E_EXECUTION_ERROR, no result): per row the WHERE is evaluated first, through
+ *     Expression::asBool, and the YIELDs only on the rows that pass.  An evaluation error in the
+ *     WHERE of any row, or in a YIELD of a passing row, fails the call.  A YIELD error on a row the
+ *     WHERE rejects is not an error.  (The reference's first-row schema probe, :318-340, evaluates
+ *     the first row's YIELDs unfiltered and reads past its record when that fails: undefined
+ *     there, unspecified here.)
+ *
+ * Expressions: a YIELD column that is exactly `$-.*' or `$var.*' expands to every input column in
+ * order (YieldClauseWrapper::prepare).  Everything nbg_go's compiler accepts over `$-' columns and
+ * constants is accepted with the same results: arithmetic, relational and logical operators, unary
+ * operators, casts between INT / DOUBLE / BOOL / TIMESTAMP, hash, the math functions, udf_is_in,
+ * comparisons of dictionary strings, now() and rand*().  `$var.x' reads the same `in' as `$-.x'.
+ * A request that references no `$-' / `$var' column at all is the reference's executeConstant (one
+ * row, whatever the input): the binding answers it without this call, which evaluates per row.
+ *
+ * Result schema: a column's kind is the compiler's static kind (input kinds are uniform per
+ * column, so this is the reference's "kind of the first row's value").  col_types follow
+ * Collector::getSchema (TraverseExecutor.cpp:163-203): the kind's own type (INT for every integer
+ * payload, so a VID or TIMESTAMP column passed through becomes INT), or, for a cast at the root of
+ * the YIELD, the cast's type; nbg_set_op's implicit casts read these types.  A constant YIELD is a
+ * constant column.  String constants outside the dictionary and the input's derived-string table
+ * are carried over, as nbg_order_by carries them.
+ * Single engine only.  yield_funs exists so that whole-input aggregates (a later change) do not
+ * alter the struct. */
+typedef struct {
+  const char* const* input_names;    /* names of `in`'s columns, as in nbg_group_request        */
+  const uint8_t* where;              /* Expression::encode bytes of WHERE; NULL/0 = none         */
+  uint32_t where_len;
+  const uint8_t* const* yield_exprs; /* Expression::encode bytes per YIELD column                */
+  const uint32_t* yield_lens;
+  const int32_t* yield_funs;         /* NBG_AGG_* per column, or NULL (all NBG_AGG_NONE)         */
+  int32_t num_yields;
+} nbg_yield_request;
+int32_t nbg_yield(nbg_engine* e, const nbg_rows* in, const nbg_yield_request* req, nbg_rows** out);
+
 /* ---- FIND SHORTEST | ALL PATH (FindPathExecutor semantics) ----------------------------- */
 typedef struct {
-  const int64_t* from;            /* de-duplicated by the callee (VerticesClause::prepare)    */
+  const int64_t* from;           /* de-duplicated by the callee (VerticesClause::prepare)    */
   uint64_t num_from;
   const int32_t* edge_types;
   int32_t num_edge_types;
@@ -680,7 +761,8 @@ typedef struct {
  * region); 0 stops timing.  Mode 1 also times nbg_order_by's launches: k_ob_iota, k_ob_hist,
  * k_ob_pick, k_ob_compact (the first-K selection), k_ob_image, ob_radix_sort, k_ob_gather,
  * k_ob_copy (DESIGN.md "ORDER BY / LIMIT"), and nbg_set_op's: k_so_insert, k_so_probe, k_so_emit,
- * k_so_copy (DESIGN.md "Set operations over device rows"). */
+ * k_so_copy (DESIGN.md "Set operations over device rows"), and nbg_yield's: k_yr_filter,
+ * k_yr_scan, k_yr_emit (DESIGN.md "YIELD over device rows"). */
 /* ---- FIND PATH replica of a partitioned engine (replica.hip) ---------------------------------
  * A partitioned engine (num_gpus > 1) also builds, at nbg_finalize (collectively), a replica of
  * every rank's path CSRs (offsets, neighbour ids and vids, ranks; no property columns) when it fits

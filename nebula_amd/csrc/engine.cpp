@@ -2668,6 +2668,289 @@ int32_t nbg_set_op(nbg_engine* h, const nbg_rows* left, const nbg_rows* right, c
   return NBG_OK;
 }
 
+// ============================================================================= YIELD ... WHERE
+// YieldExecutor::executeInputs (src/graph/YieldExecutor.cpp:178-282) over a device-resident result;
+// the kernels are in yieldrows.hip and, beside the interpreter, kernels.hip.
+namespace {
+
+// what a WHERE / YIELD tree references (ExpressionContext's has*Prop and variables())
+struct YrRefs {
+  bool graph = false;                    // $^, $$ or an edge property
+  bool input = false;
+  std::set<std::string> vars;
+  std::vector<std::string> props;        // $- / $var column names, in evaluation order
+};
+void yr_refs(const Node& n, YrRefs* r) {
+  switch (n.kind) {
+    case EK_SRCPROP: case EK_DSTPROP: case EK_ALIAS: case EK_RANK: case EK_DST: case EK_SRCID: case EK_TYPE:
+      r->graph = true;
+      break;
+    case EK_INPUT:
+      r->input = true;
+      r->props.push_back(n.prop);
+      break;
+    case EK_VAR:
+      r->vars.insert(n.alias);
+      r->props.push_back(n.prop);
+      break;
+    default: break;
+  }
+  for (auto& k : n.kids)
+    if (k) yr_refs(*k, r);
+}
+
+}  // namespace
+
+int32_t nbg_yield(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq, nbg_rows** out) {
+  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  // ---- 1. arguments
+  if (rq->num_yields < 1) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: no YIELD column");
+  if (!rq->input_names || !rq->yield_exprs || !rq->yield_lens) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: null argument");
+  if (in->eng != &E) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: the rows belong to another engine");
+  if (!in->on_device) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: the rows are host-only (not a device result)");
+  const int nc = in->ncols;
+  std::vector<std::string> names;
+  for (int c = 0; c < nc; ++c) {
+    if (!rq->input_names[c]) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: null input column name");
+    names.emplace_back(rq->input_names[c]);
+  }
+  std::string err;
+  std::unique_ptr<Node> where;
+  if (rq->where && rq->where_len) {
+    where = decode_expr(rq->where, rq->where_len, &err);
+    if (!where) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: WHERE: " + err);
+  }
+  std::vector<std::unique_ptr<Node>> given;
+  for (int y = 0; y < rq->num_yields; ++y) {
+    if (!rq->yield_exprs[y] || !rq->yield_lens[y]) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: an empty expression");
+    given.push_back(decode_expr(rq->yield_exprs[y], rq->yield_lens[y], &err));
+    if (!given.back()) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: " + err);
+    if (rq->yield_funs && (rq->yield_funs[y] < NBG_AGG_NONE || rq->yield_funs[y] > NBG_AGG_BIT_XOR))
+      return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: unknown function");
+  }
+  // ---- 2.
+  if (E.partitioned()) return E.fail(NBG_E_UNSUPPORTED, "YIELD on a partitioned engine (its rows live on several ranks)");
+  // ---- `$-.*' / `$var.*' (YieldClauseWrapper::prepare): every input column, in order
+  std::vector<std::unique_ptr<Node>> yields;
+  std::vector<int32_t> funs;
+  YrRefs refs;
+  if (where) yr_refs(*where, &refs);
+  for (int y = 0; y < rq->num_yields; ++y) {
+    Node& n = *given[y];
+    const int32_t f = rq->yield_funs ? rq->yield_funs[y] : NBG_AGG_NONE;
+    if ((n.kind == EK_INPUT || n.kind == EK_VAR) && n.prop == "*") {
+      if (n.kind == EK_INPUT) refs.input = true;
+      else refs.vars.insert(n.alias);
+      for (int c = 0; c < nc; ++c) {
+        auto col = std::make_unique<Node>();
+        col->kind = n.kind;
+        col->alias = n.alias;
+        col->prop = names[c];
+        yields.push_back(std::move(col));
+        funs.push_back(f);
+      }
+      continue;
+    }
+    yr_refs(n, &refs);
+    yields.push_back(std::move(given[y]));
+    funs.push_back(f);
+  }
+  const int ny = (int)yields.size();
+  // ---- 3. checkAggFun (:33-58), syntaxCheck (:116-122)
+  bool agg = false;
+  for (int32_t f : funs) agg = agg || f != NBG_AGG_NONE;
+  if (agg)
+    for (int y = 0; y < ny; ++y)
+      if ((yields[y]->kind == EK_INPUT || yields[y]->kind == EK_VAR) && funs[y] == NBG_AGG_NONE)
+        return E.fail(NBG_E_SYNTAX_ERROR,
+                      "Input columns without aggregation are not supported in YIELD statement without GROUP BY, near `" +
+                          yields[y]->prop + "'");
+  if (refs.graph) return E.fail(NBG_E_SYNTAX_ERROR, "Only support input and variable in yield sentence.");
+  // ---- 4. (:124-135)
+  if (refs.input && !refs.vars.empty()) return E.fail(NBG_E_EXECUTION_ERROR, "Not support both input and variable.");
+  if (refs.vars.size() > 1) return E.fail(NBG_E_EXECUTION_ERROR, "Only one variable allowed to use.");
+  // ---- 5. no rows: one column per YIELD
+  if (!in->count) {
+    *out = gb_new_rows(E, std::min(ny, (int)MAX_YIELDS));
+    return NBG_OK;
+  }
+  // ---- 6. getOutputSchema (:298-316): getFieldIndex, the first column of that name
+  auto find_col = [&](const std::string& n) {
+    auto it = std::find(names.begin(), names.end(), n);
+    return it == names.end() ? -1 : (int)(it - names.begin());
+  };
+  for (const std::string& p : refs.props)
+    if (find_col(p) < 0)
+      return E.fail(NBG_E_EXECUTION_ERROR,
+                    "column `" + p + "' not exist in " + (refs.vars.empty() ? "input." : "variable."));
+  // ---- 7. device scope
+  if (agg) return E.fail(NBG_E_UNSUPPORTED, "YIELD: aggregate functions without GROUP BY");
+  if (in->misaligned || in->float_col)
+    return E.fail(NBG_E_UNSUPPORTED, "YIELD: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (ny > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "YIELD: more than NBG_MAX_YIELDS columns");
+  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: the rows have no columns");
+  if (in->count > 0xFFFFFFFFull) return E.fail(NBG_E_UNSUPPORTED, "YIELD: an input of 2^32 rows or more");
+  std::vector<VKind> kinds(nc, VK_INT);
+  std::vector<uint8_t> outside(nc, 0), respelt(nc, 0);   // string columns: beyond the dictionary; spelt per OVER type
+  std::vector<std::string> spell(nc);
+  for (int c = 0; c < nc; ++c) {
+    const int k = in->col_kind(c);
+    kinds[c] = k < 0 ? VK_INT : (VKind)k;
+    bool have = false;
+    for (auto& cs : in->const_str) {
+      if ((int)cs.size() <= c) continue;
+      respelt[c] = respelt[c] || (have && spell[c] != cs[c]);
+      spell[c] = cs[c];
+      have = true;
+      outside[c] = outside[c] || !cs[c].empty();
+    }
+    outside[c] = outside[c] || !in->derived.empty();
+  }
+  // a use: `bare' is a YIELD column that is exactly the input column
+  auto check_use = [&](int c, bool bare) -> int32_t {
+    if (in->col_kind(c) < 0) return E.fail(NBG_E_UNSUPPORTED, "YIELD: column `" + names[c] + "' mixes value kinds");
+    if (kinds[c] != VK_STRING) return NBG_OK;
+    if (!bare && outside[c])
+      return E.fail(NBG_E_UNSUPPORTED, "YIELD: column `" + names[c] + "' can hold strings outside the dictionary");
+    if (bare && respelt[c])
+      return E.fail(NBG_E_UNSUPPORTED, "YIELD: column `" + names[c] + "' spells different constants per OVER type");
+    return NBG_OK;
+  };
+  {
+    YrRefs wr;
+    if (where) yr_refs(*where, &wr);
+    for (const std::string& p : wr.props)
+      if (int32_t rc = check_use(find_col(p), false)) return rc;
+    for (int y = 0; y < ny; ++y) {
+      const bool bare = yields[y]->kind == EK_INPUT || yields[y]->kind == EK_VAR;
+      YrRefs yr;
+      yr_refs(*yields[y], &yr);
+      for (const std::string& p : yr.props)
+        if (int32_t rc = check_use(find_col(p), bare)) return rc;
+    }
+  }
+  // ---- compile: WHERE first, then the YIELDs, one program for every row
+  static const std::vector<int32_t> no_over;
+  if (E.max_dict_len_of != E.snap.strings.size()) {
+    E.max_dict_len = 0;
+    for (const std::string& x : E.snap.strings) E.max_dict_len = std::max<uint64_t>(E.max_dict_len, x.size());
+    E.max_dict_len_of = E.snap.strings.size();
+  }
+  CompileEnv cenv{};
+  cenv.etype = 0;
+  cenv.over = &no_over;
+  cenv.edges = &E.edges;
+  cenv.strings = &E.snap.strings;
+  cenv.tags = &E.tags;
+  cenv.input_names = &names;
+  cenv.input_kinds = &kinds;
+  cenv.max_dict_len = E.max_dict_len;
+  cenv.rows = true;
+  ProgramBuilder pb;
+  YrPlan plan;
+  plan.ncols = ny;
+  bool where_false = false;
+  auto scope = [&](int32_t rc) { return E.fail(rc, "YIELD: " + err); };
+  if (where) {
+    Compiled c;
+    if (int32_t rc = compile_expr(*where, cenv, pb, &c, &err)) return scope(rc);
+    if (c.is_const) {
+      bool tv;
+      switch (c.kind) {   // Expression::asBool
+        case VK_STRING: tv = c.const_str.empty(); break;
+        case VK_DOUBLE: { double d; memcpy(&d, &c.const_bits, 8); tv = d != 0.0; break; }
+        default: tv = c.const_bits != 0;
+      }
+      where_false = !tv;
+      pb.code.clear();
+    } else {
+      const int r = c.reg;
+      if (c.kind == VK_INT) pb.code.push_back(Ins{OP_TRUTHY_I, (uint8_t)r, (uint8_t)r, 0, 0, 0});
+      else if (c.kind == VK_DOUBLE) pb.code.push_back(Ins{OP_TRUTHY_F, (uint8_t)r, (uint8_t)r, 0, 0, 0});
+      else if (c.kind == VK_STRING)
+        pb.code.push_back(Ins{OP_TRUTHY_S, (uint8_t)r, (uint8_t)r, 0, 0, string_code(E.snap.strings, "")});
+      plan.where_len = (int)pb.code.size();
+      plan.where_reg = r;
+    }
+    pb.next_reg = 0;   // WHERE registers are dead once its value is read
+  }
+  std::unique_ptr<nbg_rows> res(gb_new_rows(E, ny));
+  res->derived = in->derived;
+  ColTypeEnv tenv;
+  tenv.input_names = &names;
+  tenv.input_kinds = &kinds;
+  std::set<int32_t> direct;   // input columns passed through without the interpreter
+  for (int y = 0; y < ny; ++y) {
+    if (yields[y]->kind == EK_INPUT || yields[y]->kind == EK_VAR) {   // a bare column: copied as it is
+      const int col = find_col(yields[y]->prop);
+      plan.yield_reg[y] = -2 - col;
+      direct.insert(col);
+      res->kinds[0][y] = kinds[col];
+      res->col_types[y] = gb_natural_type(kinds[col]);
+      if (kinds[col] == VK_STRING) res->const_str[0][y] = spell[col];
+      continue;
+    }
+    Compiled c;
+    if (int32_t rc = compile_expr(*yields[y], cenv, pb, &c, &err, true)) return scope(rc);
+    plan.yield_reg[y] = c.is_const ? -1 : c.reg;
+    plan.yield_const[y] = c.is_const ? c.const_bits : 0;
+    res->kinds[0][y] = c.kind;
+    // Collector::getSchema: the value's own type, or a root cast's (yield_column_type's cast rule)
+    res->col_types[y] = yields[y]->kind == EK_CAST ? yield_column_type(*yields[y], tenv) : gb_natural_type(c.kind);
+    if (c.is_const && c.kind == VK_STRING && (c.const_bits & 1)) res->const_str[0][y] = c.const_str;
+  }
+  plan.code = pb.code;
+  plan.data = pb.data;
+  plan.nregs = std::max(1, pb.max_reg);
+  for (const Ins& i : plan.code)
+    if (i.op == OP_SOUT || i.op == OP_SMAT) return E.fail(NBG_E_UNSUPPORTED, "YIELD: an expression that builds a string");
+  if ((int)(plan.code.size() + plan.data.size()) > MAX_PROGRAM) return E.fail(NBG_E_UNSUPPORTED, "YIELD: program too long");
+  if (plan.nregs > interp_max_regs())
+    return E.fail(NBG_E_UNSUPPORTED, "YIELD: expression too deep for the device register file (" + std::to_string(plan.nregs) +
+                                         " registers, " + std::to_string(interp_max_regs()) + " fit the LDS)");
+  if (where_false) {   // a constant-false WHERE: no row, no launch
+    *out = res.release();
+    return NBG_OK;
+  }
+  {
+    std::set<int32_t> wc, yc = direct;
+    for (int pc = 0; pc < (int)plan.code.size(); ++pc)
+      if (plan.code[pc].op == OP_COL) (pc < plan.where_len ? wc : yc).insert(plan.code[pc].aux);
+    plan.where_cols = (int)wc.size();
+    plan.yield_cols = (int)yc.size();
+  }
+  // ---- 8. the passes
+  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+  plan.str = E.dev_strings();
+  plan.now_sec = (int64_t)time(nullptr);
+  plan.rand_seed = query_rand_seed();
+  auto* m = const_cast<nbg_rows*>(in);
+  m->build_segs();
+  std::vector<std::pair<uint64_t, uint64_t>> segs;
+  for (auto& sg : m->segs)
+    if (sg.end > sg.begin) segs.emplace_back(sg.begin, sg.end - sg.begin);
+  Workspace* inw = in->owned_ws ? in->owned_ws : in->ws;
+  if (!inw) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: the rows have no device workspace");
+  Workspace* ow = nullptr;
+  uint64_t n = 0;
+  if (int32_t rc = ws_yield_rows(inw, E.stream, segs, plan, &ow, &n, &E.yr_prof, &err)) return E.fail(rc, err);
+  if (ow) {
+    res->ws = res->owned_ws = ow;
+    res->count = n;
+    nbg_rows::TypeBlocks tb;
+    tb.region = 0;
+    tb.blk_cap = n;
+    tb.counts.assign(1, (uint32_t)n);
+    res->blocks.push_back(std::move(tb));
+    for (int c = 0; c < ny; ++c) res->dcols.push_back(ws_row_col(ow, c));
+  }
+  *out = res.release();
+  return NBG_OK;
+}
+
 int32_t nbg_set_path_replica(nbg_engine* h, int32_t mode) {
   if (!h || mode < 0 || mode > 1) return NBG_E_INVALID_ARGUMENT;
   Engine& E = h->e;
@@ -2694,6 +2977,8 @@ int32_t nbg_profile(nbg_engine* h, int32_t enable) {
   E.ob_prof.on = mode == 1;
   if (mode) E.so_prof = SoProf{};
   E.so_prof.on = mode == 1;
+  if (mode) E.yr_prof = YrProf{};
+  E.yr_prof.on = mode == 1;
   // the one-pair SHORTEST contexts (device-driven chains): their launches and algorithmic bytes
   for (Engine* P : {&E, E.rep.get()}) {   // (and the FIND PATH replica's)
     if (!P) continue;
@@ -2733,6 +3018,12 @@ int32_t nbg_profile_read(const nbg_engine* h, nbg_kernel_stat* out, int32_t cap)
     out[n].launches = E.so_prof.launches[k];
     out[n].total_ms = E.so_prof.ms[k];
     out[n].algo_bytes = E.so_prof.bytes[k];
+  }
+  for (int k = 0; k < YR_KINDS && n < cap; ++k, ++n) {   // nbg_yield's kernels (yieldrows.hip)
+    out[n].name = kYrKernelNames[k];
+    out[n].launches = E.yr_prof.launches[k];
+    out[n].total_ms = E.yr_prof.ms[k];
+    out[n].algo_bytes = E.yr_prof.bytes[k];
   }
   return n;
 }

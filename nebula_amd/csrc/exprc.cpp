@@ -765,7 +765,7 @@ struct Ctx {
         Compiled c;
         c.kind = (*env.input_kinds)[col];
         c.reg = push();
-        emit(OP_INPUT, c.reg, 0, 0, col);
+        emit(env.rows ? OP_COL : OP_INPUT, c.reg, 0, 0, col);
         if (c.kind == VK_STRING && env.input_derived) c = derived_of({Piece{PC_DICT, c.reg, {}}});
         *out = c;
         return NBG_OK;

@@ -54,6 +54,10 @@ struct CompileEnv {
   // read as derived strings, so compares, casts and YIELDs work on their bytes
   bool input_derived = false;
   uint64_t max_dict_len = 0;   // the longest dictionary string (bounds a derived string's bytes)
+  // rows mode (nbg_yield): the program runs per input ROW, not per edge.  $-.col / $var.col is a
+  // direct load of column aux at the lane's row: OP_COL with ExpandArgs::props = the row column
+  // bases and EdgeCtx::j = the physical row (no index search as OP_INPUT's)
+  bool rows = false;
 };
 
 // One piece of a derived string (a STRING value built on the device: concatenation, casts to

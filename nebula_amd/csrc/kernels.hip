@@ -31,6 +31,7 @@
 #include <cstring>
 #include <vector>
 
+#include "stage.h"
 #include "ws.h"
 
 namespace nbg {
@@ -1049,6 +1050,121 @@ __device__ __forceinline__ void run_program(const Ins* __restrict__ prog, const 
     }
     regs[ins.d * BLOCK + tid] = r;
   }
+}
+
+// ----------------------------------------------------------------------------- k_yr_filter / k_yr_emit
+// nbg_yield's row kernels (driven by yieldrows.hip): the program was compiled in rows mode, so a
+// $- / $var column is OP_COL over the row column bases with EdgeCtx::j = the lane's physical row.
+// One workgroup per chunk of at most OB_CHUNK rows (stage.h), grid-strided; registers in dynamic
+// LDS as k_expand's, [nregs][BLOCK] x 8 B.
+__device__ __forceinline__ ExpandArgs yr_expand_args(const YrArgs& y) {
+  ExpandArgs a{};
+  a.props = y.cols;
+  a.str = y.str;
+  a.now_sec = y.now_sec;
+  a.rand_seed = y.rand_seed;
+  return a;
+}
+
+// the WHERE per row: one keep byte per logical row, one count per chunk (a plain store)
+__global__ void __launch_bounds__(BLOCK) k_yr_filter(YrArgs y) {
+  extern __shared__ int64_t regs[];   // [nregs][BLOCK]
+  __shared__ uint32_t wcnt[WAVES];
+  const ExpandArgs a = yr_expand_args(y);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  bool any_err = false;
+  for (uint32_t k = blockIdx.x; k < y.nchunks; k += gridDim.x) {
+    const uint64_t b = y.chunk[3 * k], len = y.chunk[3 * k + 1], lo = y.chunk[3 * k + 2];
+    uint32_t mine = 0;   // (wave-uniform)
+    for (uint64_t c0 = 0; c0 < len; c0 += BLOCK) {
+      const uint64_t i = c0 + threadIdx.x;
+      const bool valid = i < len;
+      bool werr = false;
+      uint32_t tbits = 0;
+      const EdgeCtx c{b + (valid ? i : 0), 0u};
+      run_program(y.prog, y.prog + y.code_len, 0, y.where_len, c, a, regs, valid, werr, tbits);
+      const bool pass = valid && !werr && regs[y.where_reg * BLOCK + threadIdx.x] != 0;
+      any_err = any_err || (valid && werr);
+      if (valid) y.keep[lo + i] = pass;
+      mine += (uint32_t)__popcll(__ballot(pass));
+    }
+    if (lane == 0) wcnt[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t t = 0;
+      for (int w = 0; w < WAVES; ++w) t += wcnt[w];
+      y.ccount[k] = t;
+    }
+    __syncthreads();   // (wcnt is rewritten for the next chunk)
+  }
+  if (__ballot(any_err) && lane == 0) atomicOr(y.err, 1ull);
+}
+
+// the YIELDs of the kept rows, every column at chunk base + rank within the chunk (k_so_emit's
+// ranks: ballot / lane_rank per wave plus the per-step wave offsets); without keep flags a row's
+// slot is its logical index
+__global__ void __launch_bounds__(BLOCK) k_yr_emit(YrArgs y) {
+  extern __shared__ int64_t regs[];   // [nregs][BLOCK]
+  constexpr int STEPS = (int)(OB_CHUNK / BLOCK);
+  __shared__ uint32_t woff[STEPS * WAVES];
+  const ExpandArgs a = yr_expand_args(y);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  bool any_err = false;
+  for (uint32_t k = blockIdx.x; k < y.nchunks; k += gridDim.x) {
+    const uint64_t b = y.chunk[3 * k], len = y.chunk[3 * k + 1], lo = y.chunk[3 * k + 2];   // len <= OB_CHUNK
+    const int steps = (int)((len < OB_CHUNK ? len : OB_CHUNK) + BLOCK - 1) / BLOCK;         // <= STEPS
+    uint64_t base = lo;
+    if (y.keep) {
+      for (int s = 0; s < steps; ++s) {
+        const uint64_t i = (uint64_t)s * BLOCK + threadIdx.x;
+        const bool take = i < len && y.keep[lo + (i < len ? i : 0)];
+        const unsigned long long bal = __ballot(take);
+        if (lane == 0) woff[s * WAVES + wave] = (uint32_t)__popcll(bal);
+      }
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        uint32_t total = 0;
+        for (int j = 0; j < steps * WAVES; ++j) {
+          const uint32_t c = woff[j];
+          woff[j] = total;
+          total += c;
+        }
+      }
+      __syncthreads();
+      base = y.cbase[k];
+    }
+    for (int s = 0; s < steps; ++s) {
+      const uint64_t i = (uint64_t)s * BLOCK + threadIdx.x;
+      const bool valid = i < len;
+      const bool take = valid && (!y.keep || y.keep[lo + i]);
+      const unsigned long long bal = __ballot(take);
+      if (!bal) continue;   // (wave-uniform)
+      const uint64_t slot = y.keep ? base + woff[s * WAVES + wave] + lane_rank(bal) : lo + i;
+      bool yerr = false;
+      uint32_t tbits = 0;
+      const EdgeCtx c{b + (valid ? i : 0), 0u};
+      if (y.where_len < y.code_len)   // (a projection of bare columns and constants has no YIELD code)
+        run_program(y.prog, y.prog + y.code_len, y.where_len, y.code_len, c, a, regs, take, yerr, tbits);
+      any_err = any_err || (take && yerr);
+      if (take && slot < y.cap)
+        for (int col = 0; col < y.ncols; ++col) {
+          // a register, the constant (-1), or input column -2 - r passed through as it is
+          const int r = y.yield_reg[col];
+          y.out[col][slot] = r >= 0 ? regs[r * BLOCK + threadIdx.x] : r == -1 ? y.yield_const[col] : y.cols[-2 - r][c.j];
+        }
+    }
+    __syncthreads();   // (woff is rewritten for the next chunk)
+  }
+  if (__ballot(any_err) && lane == 0) atomicOr(y.err, 1ull);
+}
+
+hipError_t launch_yr_filter(const YrArgs& a, int nregs, unsigned grid, hipStream_t s) {
+  hipLaunchKernelGGL(k_yr_filter, dim3(grid), dim3(BLOCK), (size_t)nregs * BLOCK * 8, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_yr_emit(const YrArgs& a, int nregs, unsigned grid, hipStream_t s) {
+  hipLaunchKernelGGL(k_yr_emit, dim3(grid), dim3(BLOCK), (size_t)nregs * BLOCK * 8, s, a);
+  return hipGetLastError();
 }
 
 // ----------------------------------------------------------------------------- k_expand

@@ -828,6 +828,62 @@ int32_t ws_set_op(Workspace* lw, Workspace* rw, hipStream_t stream,
                   const std::vector<std::pair<uint64_t, uint64_t>>& rsegs, const SoPlan& plan, Workspace** outw,
                   uint64_t* rows, SoProf* prof, std::string* err);
 
+// ---- YIELD ... WHERE over device rows (yieldrows.hip; YieldExecutor.cpp:178-282).  One program
+// compiled in CompileEnv's rows mode (WHERE first, then the YIELDs) and run per row.
+struct YrPlan {
+  std::vector<Ins> code;            // WHERE ([0, where_len)), then the YIELDs
+  std::vector<Ins> data;            // piece lists and constant bytes (after `code` on the device)
+  int where_len = 0;
+  int where_reg = -1;               // register holding asBool(WHERE); -1: no WHERE (every row passes)
+  int nregs = 1;
+  int ncols = 0;
+  int yield_reg[MAX_YIELDS] = {};   // register per result column; -1: the constant yield_const;
+                                    // -2 - c: input column c as it is (a bare `$-.col' skips the interpreter)
+  int64_t yield_const[MAX_YIELDS] = {};
+  int where_cols = 0, yield_cols = 0;   // distinct input columns each part reads (profiling bytes)
+  DevStrings str;                   // the dictionary's device tables
+  int64_t now_sec = 0;
+  uint64_t rand_seed = 0;
+};
+// nbg_profile_read's YIELD entries (kYrKernelNames), timed while nbg_profile mode 1 is on
+enum YrKernel { YR_K_FILTER = 0, YR_K_SCAN, YR_K_EMIT, YR_KINDS };
+extern const char* const kYrKernelNames[YR_KINDS];
+struct YrProf {
+  bool on = false;
+  uint64_t launches[YR_KINDS] = {};
+  double ms[YR_KINDS] = {};
+  double bytes[YR_KINDS] = {};
+};
+// The row kernels sit beside the interpreter (kernels.hip); yieldrows.hip drives them.
+// chunk: stage_chunks' list on the device; cols: the input's column bases (device array).
+struct YrArgs {
+  const uint64_t* chunk;
+  uint32_t nchunks;
+  const int64_t* const* cols;
+  const Ins* prog;                  // code, then data
+  int code_len, where_len, where_reg;
+  uint8_t* keep;                    // one byte per logical row (nullptr: every row is kept)
+  uint32_t* ccount;                 // filter: kept rows per chunk
+  const uint32_t* cbase;            // emit: the first result row of each chunk's kept rows
+  unsigned long long* err;          // evaluation errors, ORed
+  int ncols;
+  int yield_reg[MAX_YIELDS];
+  int64_t yield_const[MAX_YIELDS];
+  int64_t* out[MAX_YIELDS];
+  uint64_t cap;                     // rows the result holds
+  DevStrings str;
+  int64_t now_sec;
+  uint64_t rand_seed;
+};
+hipError_t launch_yr_filter(const YrArgs& a, int nregs, unsigned grid, hipStream_t s);
+hipError_t launch_yr_emit(const YrArgs& a, int nregs, unsigned grid, hipStream_t s);
+// Filters and projects the rows of `inw` listed by segs (first row, rows) into a fresh rows-only
+// workspace on `stream` (*outw; nullptr when no row passes) of *rows rows, in the input's order.
+// Synchronous; every scratch allocation is released before it returns.  NBG_OK,
+// NBG_E_EXECUTION_ERROR (an evaluation error), NBG_E_OUT_OF_MEMORY or NBG_E_DEVICE.
+int32_t ws_yield_rows(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
+                      const YrPlan& plan, Workspace** outw, uint64_t* rows, YrProf* prof, std::string* err);
+
 // Query pipeline (all asynchronous on the workspace stream until ws_end_query):
 hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, const std::vector<TypeProgram>* progs,
                           uint64_t stmt_id);

@@ -1,0 +1,184 @@
+// nebula_amd — piped YIELD ... WHERE over a device-resident result (gfx950, wave64).
+// YieldExecutor::executeInputs (src/graph/YieldExecutor.cpp:178-282) over the row segments earlier
+// stages leave in HBM.  One program (WHERE first, then the YIELDs), compiled in CompileEnv's rows
+// mode, runs per row through the GO interpreter; the kernels that call it sit beside it in
+// kernels.hip (launch_yr_filter, launch_yr_emit):
+//   k_yr_filter   the WHERE per row: one keep byte per logical row, one count per chunk
+//   k_yr_scan     exclusive scan of the chunk counts into chunk bases and the total (one workgroup)
+//   k_yr_emit     the YIELDs of the kept rows, stored at chunk base + rank within the chunk, so the
+//                 result keeps the input's fetch order
+// Without a WHERE the first two are skipped and a row's slot is its logical index.  The input is
+// walked through the chunk list of stage.h, one workgroup per chunk.  No kernel waits on another
+// workgroup: every dependency is a kernel boundary on one stream.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "stage.h"
+#include "ws.h"
+
+namespace nbg {
+
+const char* const kYrKernelNames[YR_KINDS] = {"k_yr_filter", "k_yr_scan", "k_yr_emit"};
+
+namespace {
+
+// what the host reads back in one copy: the kept rows and the evaluation errors
+struct YrState {
+  unsigned long long total, err;
+};
+
+// base[k] = sum of count[0..k), st->total = the sum of all; each thread scans a contiguous slice
+__global__ void __launch_bounds__(BLOCK) k_yr_scan(const uint32_t* __restrict__ count, uint32_t n,
+                                                   uint32_t* __restrict__ base, YrState* __restrict__ st) {
+  __shared__ uint32_t lds[WAVES];
+  const uint32_t per = (n + BLOCK - 1) / BLOCK;
+  const uint64_t first = (uint64_t)threadIdx.x * per;
+  const uint32_t lo = first < n ? (uint32_t)first : n;
+  const uint32_t hi = first + per < n ? (uint32_t)(first + per) : n;
+  uint32_t sum = 0;
+  for (uint32_t i = lo; i < hi; ++i) sum += count[i];
+  uint32_t total = 0;
+  uint32_t run = block_excl_scan(sum, &total, lds);
+  for (uint32_t i = lo; i < hi; ++i) {
+    base[i] = run;
+    run += count[i];
+  }
+  if (threadIdx.x == 0) st->total = total;
+}
+
+}  // namespace
+
+int32_t ws_yield_rows(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
+                      const YrPlan& plan, Workspace** outw, uint64_t* rows, YrProf* prof, std::string* err) {
+  *outw = nullptr;
+  *rows = 0;
+  hipError_t he = hipSuccess;
+  const char* what = "";
+  auto failed = [&](hipError_t e, const char* w) {
+    he = e;
+    what = w;
+    return e != hipSuccess;
+  };
+  auto code = [&]() -> int32_t {
+    if (err) *err = std::string("YIELD: ") + what + ": " + hipGetErrorString(he);
+    return he == hipErrorOutOfMemory ? NBG_E_OUT_OF_MEMORY : NBG_E_DEVICE;
+  };
+  uint64_t n = 0;
+  for (auto& sg : segs) n += sg.second;
+  if (plan.ncols < 1 || plan.ncols > MAX_YIELDS || !n || n > 0xFFFFFFFFull || plan.code.size() + plan.data.size() > (size_t)MAX_PROGRAM ||
+      plan.where_len < 0 || (size_t)plan.where_len > plan.code.size() || (plan.where_reg >= 0) != (plan.where_len > 0) ||
+      plan.where_reg >= plan.nregs) {
+    if (err) *err = "YIELD: empty input or plan";
+    return NBG_E_INVALID_ARGUMENT;
+  }
+
+  // the result: a workspace holding nothing but its rows (what the row accessors read)
+  struct WsGuard {
+    Workspace* w = nullptr;
+    ~WsGuard() { if (w) ws_destroy(w); }
+  } res;
+  auto new_result = [&](uint64_t nout) {
+    res.w = new Workspace();
+    res.w->stream = stream;
+    hipError_t e = hipMalloc((void**)&res.w->d_row_cols, MAX_YIELDS * sizeof(int64_t*));
+    if (e == hipSuccess) e = ws_reserve_rows(res.w, nout, plan.ncols);
+    if (e != hipSuccess) (void)hipGetLastError();
+    return e;
+  };
+
+  StageScratch sc;   // (declared before the timer: the timer's events are resolved first)
+  StageTimer<YrProf> tm{prof, stream, {}, nullptr};
+  const std::vector<uint64_t> chunks = stage_chunks(segs, 0, n);
+  const uint32_t nchunks = (uint32_t)(chunks.size() / 3);
+  const unsigned grid = std::min<unsigned>(std::max<uint32_t>(nchunks, 1), STAGE_GRID);
+  std::vector<Ins> image(plan.code);
+  image.insert(image.end(), plan.data.begin(), plan.data.end());
+  uint64_t* d_chunks = nullptr;
+  Ins* d_prog = nullptr;
+  YrState* st = nullptr;
+  // (a pageable source is staged by the runtime before the call returns)
+  if (failed(sc.alloc((void**)&d_chunks, chunks.size() * 8), "chunk list") ||
+      failed(sc.alloc((void**)&d_prog, image.size() * sizeof(Ins)), "program") ||
+      failed(sc.alloc((void**)&st, sizeof(YrState)), "state") ||
+      failed(hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * 8, hipMemcpyHostToDevice, stream), "chunk upload") ||
+      (!image.empty() &&
+       failed(hipMemcpyAsync(d_prog, image.data(), image.size() * sizeof(Ins), hipMemcpyHostToDevice, stream), "program upload")) ||
+      failed(hipMemsetAsync(st, 0, sizeof(YrState), stream), "state clear") ||
+      failed(hipStreamSynchronize(stream), "uploads"))
+    return code();
+
+  YrArgs a{};
+  a.chunk = d_chunks;
+  a.nchunks = nchunks;
+  a.cols = (const int64_t* const*)inw->d_row_cols;
+  a.prog = d_prog;
+  a.code_len = (int)plan.code.size();
+  a.where_len = plan.where_len;
+  a.where_reg = plan.where_reg;
+  a.err = &st->err;
+  a.ncols = plan.ncols;
+  for (int c = 0; c < plan.ncols; ++c) {
+    a.yield_reg[c] = plan.yield_reg[c];
+    a.yield_const[c] = plan.yield_const[c];
+  }
+  a.str = plan.str;
+  a.now_sec = plan.now_sec;
+  a.rand_seed = plan.rand_seed;
+
+  uint64_t nout = n;
+  YrState got{};
+  if (plan.where_reg >= 0) {
+    uint32_t* ccount = nullptr;
+    uint32_t* cbase = nullptr;
+    if (failed(sc.alloc((void**)&a.keep, n), "keep flags") || failed(sc.alloc((void**)&ccount, (size_t)nchunks * 4), "chunk counts") ||
+        failed(sc.alloc((void**)&cbase, (size_t)nchunks * 4), "chunk bases"))
+      return code();
+    a.ccount = ccount;
+    a.cbase = cbase;
+    tm.begin();
+    he = launch_yr_filter(a, plan.nregs, grid, stream);
+    tm.end(YR_K_FILTER, (double)n * (8.0 * plan.where_cols + 1.0));
+    if (failed(he, "k_yr_filter")) return code();
+    tm.begin();
+    hipLaunchKernelGGL(k_yr_scan, dim3(1), dim3(BLOCK), 0, stream, ccount, nchunks, cbase, st);
+    tm.end(YR_K_SCAN, (double)nchunks * 8.0);
+    if (failed(hipGetLastError(), "k_yr_scan") ||
+        failed(hipMemcpyAsync(&got, st, sizeof(YrState), hipMemcpyDeviceToHost, stream), "kept rows read") ||
+        failed(hipStreamSynchronize(stream), "filter"))
+      return code();
+    if (got.err) {
+      if (err) *err = "YIELD: an evaluation error in the WHERE clause";
+      return NBG_E_EXECUTION_ERROR;
+    }
+    nout = got.total;
+    if (nout > n) {
+      if (err) *err = "YIELD: " + std::to_string(nout) + " rows kept of " + std::to_string(n);
+      return NBG_E_DEVICE;
+    }
+    if (!nout) return NBG_OK;
+  }
+
+  if (failed(new_result(nout), "result rows")) return code();
+  for (int c = 0; c < plan.ncols; ++c) a.out[c] = ws_row_col(res.w, c);
+  a.cap = nout;
+  tm.begin();
+  he = launch_yr_emit(a, plan.nregs, grid, stream);
+  tm.end(YR_K_EMIT, (double)n * (a.keep ? 1.0 : 0.0) + (double)nout * 8.0 * (plan.yield_cols + plan.ncols));
+  if (failed(he, "k_yr_emit") || failed(hipMemcpyAsync(&got, st, sizeof(YrState), hipMemcpyDeviceToHost, stream), "error word read") ||
+      failed(hipStreamSynchronize(stream), "emission"))
+    return code();
+  if (got.err) {
+    if (err) *err = "YIELD: an evaluation error in a YIELD column";
+    return NBG_E_EXECUTION_ERROR;
+  }
+  *outw = res.w;
+  res.w = nullptr;
+  *rows = nout;
+  return NBG_OK;
+}
+
+}  // namespace nbg

@@ -431,6 +431,27 @@ class Engine:
         self._check(self.lib.nbg_set_op(self.h, left.h, right.h, C.byref(req), C.byref(out)), "set_op")
         return DeviceRows(self, out)
 
+    def yield_rows(self, rows: DeviceRows, input_names, yields, where=b"", funs=None) -> DeviceRows:
+        """nbg_yield: ``| YIELD yields WHERE where`` over a device-resident result.  ``input_names``
+        names ``rows``' columns, ``yields`` holds Expression::encode bytes per YIELD column (``$-.*``
+        expands to every input column), ``where`` those of the WHERE (empty: none) and ``funs`` is
+        None or one NBG_AGG_* value or name per column.  The result is a new DeviceRows in the
+        input's row order, filtered; ``rows`` stays valid and unchanged."""
+        names = (C.c_char_p * max(1, len(input_names)))(*[n.encode() for n in input_names])
+        bufs = [np.frombuffer(bytes(b), np.uint8).copy() for b in yields]
+        ptrs = (C.POINTER(C.c_uint8) * max(1, len(bufs)))(*[b.ctypes.data_as(C.POINTER(C.c_uint8)) for b in bufs])
+        lens = (C.c_uint32 * max(1, len(bufs)))(*[len(b) for b in bufs])
+        wbuf = np.frombuffer(bytes(where), np.uint8).copy()
+        wptr = wbuf.ctypes.data_as(C.POINTER(C.c_uint8)) if len(wbuf) else None
+        fptr = None
+        if funs is not None:
+            fptr = (C.c_int32 * max(1, len(funs)))(*[L.AGG_BY_NAME[f.upper()] if isinstance(f, str) else int(f)
+                                                     for f in funs])
+        req = L.nbg_yield_request(names, wptr, len(wbuf), ptrs, lens, fptr, len(bufs))
+        out = C.c_void_p()
+        self._check(self.lib.nbg_yield(self.h, rows.h, C.byref(req), C.byref(out)), "yield_rows")
+        return DeviceRows(self, out)
+
     def default_columns(self, etypes, over_all=False):
         """Edge types of a YIELD-less GO's `<edge>._dst` columns, in column order (OVER order;
         for OVER *, the response edge_schema's iteration order, GoExecutor.cpp:481-499)."""
