@@ -23,6 +23,8 @@
  *       src/graph/LimitExecutor.cpp:18-66)
  *   nbg_set_op                 ≙ SetExecutor (src/graph/SetExecutor.cpp:98-383)
  *   nbg_yield                  ≙ YieldExecutor over piped rows (src/graph/YieldExecutor.cpp:178-282)
+ *   nbg_fetch_vertices         ≙ FetchVerticesExecutor over piped rows or a vid list
+ *       (src/graph/FetchVerticesExecutor.cpp:19-311, src/graph/FetchExecutor.cpp:14-131)
  *   nbg_get_neighbors          ≙ StorageServiceHandler::future_getBound → QueryBoundProcessor
  *       (src/storage/StorageServiceHandler.cpp:33-40, src/storage/QueryBoundProcessor.cpp:16-220)
  */
@@ -104,6 +106,17 @@ extern "C" {
  *   an input whose row schema re-reads its columns (a misaligned or FLOAT column);
  *   more than NBG_MAX_YIELDS columns after `$-.*' expansion; a program over 256 instructions or
  *   over the interpreter's register limit; an input of 2^32 rows or more.
+ * nbg_fetch_vertices (tests/test_gpu_fetch.py holds one test per limit a GO result can reach; the
+ * mixed-kind vid column, the missing tag tables and the row count are guards no test reaches):
+ *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
+ *   an input whose row schema re-reads its columns (a misaligned or FLOAT column);
+ *   a vid column whose value kind differs between OVER types (col_kind == -1);
+ *   a YIELD that builds a string (concatenation, a cast to string, string functions);
+ *   any prop for which nbg_go's compiler answers `$^.tag.prop' with NBG_E_UNSUPPORTED (a tag
+ *   without device tables); a bare FLOAT prop (the result would carry a FLOAT column; below the
+ *   root of an expression a FLOAT prop is accepted and reads as its double, a DOUBLE column);
+ *   more than NBG_MAX_YIELDS columns; a program over 256 instructions or over the interpreter's
+ *   register limit; an input of 2^32 rows or more.
  * (A storage filter with a function call is E_INVALID_FILTER per part, as checkExp answers it,
  * QueryBaseProcessor.inl:172-290.)
  * Not limits: $- / $var input strings absent from the snapshot's dictionary, string functions
@@ -614,6 +627,84 @@ typedef struct {
 } nbg_yield_request;
 int32_t nbg_yield(nbg_engine* e, const nbg_rows* in, const nbg_yield_request* req, nbg_rows** out);
 
+/* ---- piped FETCH PROP ON <tag> over a device-resident result (FetchVerticesExecutor) ----------
+ * `| FETCH PROP ON player $-.id YIELD player.name, player.age` over rows in HBM
+ * (FetchVerticesExecutor.cpp:19-311, FetchExecutor.cpp:14-131).  Input and output follow
+ * nbg_yield's contract: `in` is a device-resident result of the same single engine (a GO result,
+ * or the output of nbg_group_by, nbg_order_by, nbg_set_op, nbg_yield or nbg_fetch_vertices itself);
+ * it stays valid and unchanged.  `out` is an ordinary device-resident nbg_rows of one segment in a
+ * workspace of its own: every nbg_rows_* accessor works on it and it feeds nbg_group_by,
+ * nbg_order_by, nbg_set_op, nbg_yield and nbg_fetch_vertices.  It carries no column names.  The
+ * call runs under the engine lock on the engine's stream; its scratch is released before it
+ * returns: 5 bytes per input row (a 4-byte dense id and a keep byte), 32 bytes per chunk of at most
+ * 2,048 rows (the 24-byte chunk list entry, a count and a base), a 16-byte state word pair and the
+ * compiled program; a literal vid list adds its temporary input of 8 bytes per vid, and `distinct`
+ * adds nbg_set_op's UNION DISTINCT scratch beside the rows not yet de-duplicated.  A failed
+ * allocation is NBG_E_OUT_OF_MEMORY.  With in == NULL the evaluated vid list `vids` of
+ * `FETCH PROP ON t 1, 2` is uploaded into a temporary one-column result and takes the same path.
+ *
+ * Rows: one result row per input row whose vid is found; duplicates are kept (getVIDs keeps them,
+ * InterimResult.cpp:29-49, and the storage client sends every occurrence).  A vid is found when it
+ * is a vertex of the snapshot, the vertex carries a decoded record of the tag, and that record lives
+ * in the part the storage client asks, uint64(vid) % num_parts + 1 (StorageClient::getVertexProps;
+ * QueryBoundProcessor::processVertex).  A live record whose value does not decode is no record
+ * here: collectProps skips every bad value (QueryBaseProcessor.inl:323-326), so no tag_data is
+ * sent, as nbg_get_neighbors has it.  A vid that is absent, without the tag, undecodable or
+ * invisible yields no row and no error (FetchVerticesTest.nonExistVertex; processResult skips empty tag_data,
+ * FetchVerticesExecutor.cpp:179-181).
+ *
+ * Row order: the input's fetch order with the missing rows removed (the reference's order is per
+ * host and part, hence unspecified), so `ORDER BY | FETCH | LIMIT` is exact.  Under `distinct`
+ * the order is unspecified.
+ *
+ * distinct (YIELD DISTINCT): the result holds each distinct output row once (processResult's
+ * uniqResult, :159, :221-228); doubles compare as in nbg_set_op.  De-duplicating the vids first
+ * (getDistinctVIDs, InterimResult.cpp:51-72; setupVidsFromExpr, :246-283) is then redundant.
+ *
+ * Expressions: `tag.prop' (an alias property whose alias is the tag's registered name) reads the
+ * found vertex's column; everything nbg_yield accepts over columns and constants is accepted with
+ * the same results.  A YIELD that is exactly `tag.prop' is copied without the interpreter.
+ *
+ * Result schema: col_types follow FetchExecutor::prepareYield (FetchExecutor.cpp:35-47): a bare
+ * `tag.prop' takes the tag schema's field type, a root cast the cast's type, anything else the
+ * value's natural type.  String cells are dictionary codes; string constants outside the
+ * dictionary are carried as nbg_yield carries them.
+ *
+ * Statuses, in this order:
+ *  1. NBG_E_INVALID_ARGUMENT: a null argument; `in` host-only or of another engine; in == NULL
+ *     with vids == NULL and num_vids > 0; expression bytes that do not decode.
+ *  2. NBG_E_UNSUPPORTED: a partitioned engine.
+ *  3. NBG_E_EXECUTION_ERROR: tag_id not registered ("tag schema not exist", :45-50); vid_col
+ *     equal to `*' (:79-81).
+ *  4. NBG_E_SYNTAX_ERROR, for an empty input too (prepareYield runs before setupVids): any `$^' /
+ *     `$$' node; any `$-' / `$var' node in a YIELD; an alias other than the tag's name
+ *     (FetchExecutor.cpp:50-68).
+ *  5. Zero input rows: NBG_OK and a zero-row result with one column per YIELD (onEmptyInputs,
+ *     FetchExecutor.cpp:99-107).
+ *  6. NBG_E_EXECUTION_ERROR: vid_col absent from input_names, or a column whose kind is not INT
+ *     or whose col_type is neither INT nor VID ("Column `x' not found": RowReader::getVid,
+ *     RowReader.cpp:569-576, refuses TIMESTAMP, DOUBLE, BOOL and STRING); no `tag.prop' anywhere
+ *     in the YIELDs ("No props declared.", :110-115); a prop the tag's latest schema lacks ("Get
+ *     props failed", :121-124).
+ *  7. Device scope: see "Device limits" (NBG_E_UNSUPPORTED; the caller then fetches the ids and
+ *     runs the reference's path).
+ *  8. An evaluation error in a YIELD of a found row: NBG_E_EXECUTION_ERROR, no result (:206-210).
+ * Single engine only.  The join is a binary search of the sorted vid table per row (DESIGN.md
+ * "FETCH PROP over device rows"). */
+typedef struct {
+  const char* const* input_names;    /* names of `in`'s columns; unused when in == NULL            */
+  const char* vid_col;               /* the `name' of `$-.name' / `$var.name'; unused when in == NULL */
+  const int64_t* vids;               /* in == NULL: the evaluated vid list of `FETCH PROP ON t 1, 2' */
+  uint64_t num_vids;
+  int32_t tag_id;                    /* the tag of `ON <tag>' (the binding resolved the name)       */
+  const uint8_t* const* yield_exprs; /* Expression::encode bytes per YIELD column                   */
+  const uint32_t* yield_lens;
+  int32_t num_yields;                /* 0: no YIELD clause: every column of the tag's latest schema,
+                                        in schema order (FetchExecutor::setupColumns)               */
+  int32_t distinct;                  /* YIELD DISTINCT                                              */
+} nbg_fetch_request;
+int32_t nbg_fetch_vertices(nbg_engine* e, const nbg_rows* in, const nbg_fetch_request* req, nbg_rows** out);
+
 /* ---- FIND SHORTEST | ALL PATH (FindPathExecutor semantics) ----------------------------- */
 typedef struct {
   const int64_t* from;           /* de-duplicated by the callee (VerticesClause::prepare)    */
@@ -762,7 +853,8 @@ typedef struct {
  * k_ob_pick, k_ob_compact (the first-K selection), k_ob_image, ob_radix_sort, k_ob_gather,
  * k_ob_copy (DESIGN.md "ORDER BY / LIMIT"), and nbg_set_op's: k_so_insert, k_so_probe, k_so_emit,
  * k_so_copy (DESIGN.md "Set operations over device rows"), and nbg_yield's: k_yr_filter,
- * k_yr_scan, k_yr_emit (DESIGN.md "YIELD over device rows"). */
+ * k_yr_scan, k_yr_emit (DESIGN.md "YIELD over device rows"), and nbg_fetch_vertices':
+ * k_fv_resolve, k_fv_emit (DESIGN.md "FETCH PROP over device rows"). */
 /* ---- FIND PATH replica of a partitioned engine (replica.hip) ---------------------------------
  * A partitioned engine (num_gpus > 1) also builds, at nbg_finalize (collectively), a replica of
  * every rank's path CSRs (offsets, neighbour ids and vids, ranks; no property columns) when it fits

@@ -50,6 +50,7 @@ static void free_edge_type(DevEdgeType& d) {
 void Engine::free_snapshot() {
   for (auto& kv : snap.types) free_edge_type(kv.second);
   for (auto& kv : snap.tags) {
+    if (kv.second.decoded && kv.second.decoded != kv.second.present) (void)hipFree(kv.second.decoded);
     if (kv.second.present) (void)hipFree(kv.second.present);
     for (auto* p : kv.second.cols)
       if (p) (void)hipFree(p);
@@ -2951,6 +2952,249 @@ int32_t nbg_yield(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq
   return NBG_OK;
 }
 
+// ============================================================================= FETCH PROP ON <tag>
+// FetchVerticesExecutor / FetchExecutor (src/graph/FetchVerticesExecutor.cpp:19-311,
+// src/graph/FetchExecutor.cpp:14-131) over a device-resident result; the kernels are in
+// fetchrows.hip and, beside the interpreter, kernels.hip.
+namespace {
+
+// what a YIELD tree of a FETCH references (ExpressionContext's has*Prop and aliasProps())
+struct FvRefs {
+  bool graph = false;   // $^ / $$
+  bool input = false;   // $- / $var
+  std::vector<std::pair<std::string, std::string>> alias;   // (alias, prop), in evaluation order
+};
+void fv_refs(const Node& n, FvRefs* r) {
+  switch (n.kind) {
+    case EK_SRCPROP: case EK_DSTPROP: r->graph = true; break;
+    case EK_INPUT: case EK_VAR: r->input = true; break;
+    case EK_ALIAS: case EK_RANK: case EK_DST: case EK_SRCID: case EK_TYPE: r->alias.emplace_back(n.alias, n.prop); break;
+    default: break;
+  }
+  for (auto& k : n.kids)
+    if (k) fv_refs(*k, r);
+}
+
+// a one-segment device result holding `n` rows in `w` (the stages' result form)
+void fv_adopt(nbg_rows* r, Workspace* w, uint64_t n, int ncols) {
+  r->ws = r->owned_ws = w;
+  r->count = n;
+  nbg_rows::TypeBlocks tb;
+  tb.region = 0;
+  tb.blk_cap = n;
+  tb.counts.assign(1, (uint32_t)n);
+  r->blocks.push_back(std::move(tb));
+  for (int c = 0; c < ncols; ++c) r->dcols.push_back(ws_row_col(w, c));
+}
+
+}  // namespace
+
+int32_t nbg_fetch_vertices(nbg_engine* h, const nbg_rows* in, const nbg_fetch_request* rq, nbg_rows** out) {
+  if (!h || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  // ---- 1. arguments
+  if (rq->num_yields < 0 || (rq->num_yields > 0 && (!rq->yield_exprs || !rq->yield_lens)))
+    return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null argument");
+  if (in) {
+    if (!rq->input_names || !rq->vid_col) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null argument");
+    if (in->eng != &E) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: the rows belong to another engine");
+    if (!in->on_device) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: the rows are host-only (not a device result)");
+  } else if (!rq->vids && rq->num_vids) {
+    return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null vid list");
+  }
+  if (!E.finalized) return E.fail(NBG_E_STATE, "engine not finalized");
+  const int nc = in ? in->ncols : 1;
+  std::vector<std::string> names;
+  if (in) {
+    for (int c = 0; c < nc; ++c) {
+      if (!rq->input_names[c]) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null input column name");
+      names.emplace_back(rq->input_names[c]);
+    }
+  } else {
+    names.emplace_back("id");
+  }
+  const std::string vid_col = in ? rq->vid_col : "id";
+  std::string err;
+  std::vector<std::unique_ptr<Node>> yields;
+  for (int y = 0; y < rq->num_yields; ++y) {
+    if (!rq->yield_exprs[y] || !rq->yield_lens[y]) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: an empty expression");
+    yields.push_back(decode_expr(rq->yield_exprs[y], rq->yield_lens[y], &err));
+    if (!yields.back()) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: " + err);
+  }
+  // ---- 2.
+  if (E.partitioned()) return E.fail(NBG_E_UNSUPPORTED, "FETCH on a partitioned engine (its rows live on several ranks)");
+  // ---- 3. prepareClauses (:39-50), prepareVids (:79-81)
+  auto tit = E.tags.find(rq->tag_id);
+  const Schema* tsc = tit == E.tags.end() ? nullptr : tit->second.latest();
+  if (!tsc) return E.fail(NBG_E_EXECUTION_ERROR, "tag " + std::to_string(rq->tag_id) + " schema not exist.");
+  const std::string& tag_name = tit->second.name;
+  if (in && vid_col == "*") return E.fail(NBG_E_EXECUTION_ERROR, "Cant not use `*' to reference a vertex id column.");
+  // ---- no YIELD clause: every column of the latest schema, in order (FetchExecutor::setupColumns, :73-90)
+  if (!rq->num_yields)
+    for (const Column& col : tsc->cols) {
+      auto n = std::make_unique<Node>();
+      n->kind = EK_ALIAS;
+      n->alias = tag_name;
+      n->prop = col.name;
+      yields.push_back(std::move(n));
+    }
+  const int ny = (int)yields.size();
+  // ---- 4. prepareYield (FetchExecutor.cpp:50-68), before setupVids: diagnosed for an empty input too
+  FvRefs refs;
+  for (auto& y : yields) fv_refs(*y, &refs);
+  if (refs.graph) return E.fail(NBG_E_SYNTAX_ERROR, "tag.prop and edgetype.prop are supported in fetch sentence.");
+  if (refs.input) return E.fail(NBG_E_SYNTAX_ERROR, "`$-' and `$variable' not supported in fetch yet.");
+  for (auto& ap : refs.alias)
+    if (ap.first != tag_name)
+      return E.fail(NBG_E_SYNTAX_ERROR,
+                    "Near [" + ap.first + "." + ap.second + "], tag or edge should be declared in statement first.");
+  // ---- 5. no rows (onEmptyInputs, FetchExecutor.cpp:99-107): one column per YIELD
+  const uint64_t nin = in ? in->count : rq->num_vids;
+  if (!nin) {
+    *out = gb_new_rows(E, std::min(ny, (int)MAX_YIELDS));
+    return NBG_OK;
+  }
+  // ---- 6. getVIDs -> RowReader::getVid (InterimResult.cpp:29-72, RowReader.cpp:569-576): INT and VID
+  // columns only; getPropNames (:142-153, :110-115); the storage request names a prop the schema lacks
+  int vcol = 0;
+  if (in) {
+    auto it = std::find(names.begin(), names.end(), vid_col);
+    vcol = it == names.end() ? -1 : (int)(it - names.begin());
+    bool ok = vcol >= 0;
+    if (ok) {
+      const int k = in->col_kind(vcol);
+      const int32_t t = vcol < (int)in->col_types.size() && in->col_types[vcol] ? in->col_types[vcol]
+                                                                                : gb_natural_type(k < 0 ? VK_INT : (VKind)k);
+      ok = (k < 0 || k == VK_INT) && (t == NBG_T_INT || t == NBG_T_VID);
+    }
+    if (!ok) return E.fail(NBG_E_EXECUTION_ERROR, "Column `" + vid_col + "' not found");
+  }
+  if (refs.alias.empty()) return E.fail(NBG_E_EXECUTION_ERROR, "No props declared.");
+  for (auto& ap : refs.alias)
+    if (tsc->find(ap.second) < 0) return E.fail(NBG_E_EXECUTION_ERROR, "Get props failed");
+  // ---- 7. device scope
+  if (in && (in->misaligned || in->float_col))
+    return E.fail(NBG_E_UNSUPPORTED, "FETCH: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (in && in->col_kind(vcol) < 0) return E.fail(NBG_E_UNSUPPORTED, "FETCH: column `" + vid_col + "' mixes value kinds");
+  if (ny > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "FETCH: more than NBG_MAX_YIELDS columns");
+  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: the rows have no columns");
+  if (nin > 0xFFFFFFFFull) return E.fail(NBG_E_UNSUPPORTED, "FETCH: an input of 2^32 rows or more");
+  auto dit = E.snap.tags.find(rq->tag_id);
+  if (dit == E.snap.tags.end() || !dit->second.decoded || !E.snap.d_tcols || !E.snap.d_tpres || !E.snap.d_vids)
+    return E.fail(NBG_E_UNSUPPORTED, "FETCH: tag tables missing");
+  const DevTag& dtag = dit->second;
+  // ---- compile: the YIELDs, one program for every found row
+  static const std::vector<int32_t> no_over;
+  if (E.max_dict_len_of != E.snap.strings.size()) {
+    E.max_dict_len = 0;
+    for (const std::string& x : E.snap.strings) E.max_dict_len = std::max<uint64_t>(E.max_dict_len, x.size());
+    E.max_dict_len_of = E.snap.strings.size();
+  }
+  CompileEnv cenv{};
+  cenv.etype = 0;
+  cenv.over = &no_over;
+  cenv.edges = &E.edges;
+  cenv.strings = &E.snap.strings;
+  cenv.tags = &E.tags;
+  cenv.dtags = &E.snap.tags;
+  cenv.max_dict_len = E.max_dict_len;
+  cenv.rows = true;
+  cenv.fetch_tag = &tag_name;
+  ProgramBuilder pb;
+  FvPlan plan;
+  plan.y.ncols = ny;
+  plan.vid_col = vcol;
+  plan.pres = dtag.decoded;
+  std::unique_ptr<nbg_rows> res(gb_new_rows(E, ny));
+  ColTypeEnv tenv;
+  std::set<int32_t> tcols_read;
+  for (int y = 0; y < ny; ++y) {
+    const Node& n = *yields[y];
+    if (n.kind == EK_ALIAS) {   // a bare `tag.prop': the found vertex's column as it is
+      const int col = tsc->find(n.prop);
+      if (col >= (int)dtag.kind.size()) return E.fail(NBG_E_UNSUPPORTED, "FETCH: tag tables missing");
+      plan.y.yield_reg[y] = -2 - (dtag.col_base + col);
+      tcols_read.insert(dtag.col_base + col);
+      res->kinds[0][y] = dtag.kind[col];
+      res->col_types[y] = tsc->cols[col].type;   // FetchExecutor::prepareYield, :37-42
+      if (res->col_types[y] == NBG_T_FLOAT) return E.fail(NBG_E_UNSUPPORTED, "FETCH: a bare FLOAT prop (a FLOAT result column)");
+      continue;
+    }
+    Compiled c;
+    if (int32_t rc = compile_expr(n, cenv, pb, &c, &err, true)) return E.fail(rc, "FETCH: " + err);
+    plan.y.yield_reg[y] = c.is_const ? -1 : c.reg;
+    plan.y.yield_const[y] = c.is_const ? c.const_bits : 0;
+    res->kinds[0][y] = c.kind;
+    res->col_types[y] = n.kind == EK_CAST ? yield_column_type(n, tenv) : gb_natural_type(c.kind);   // :43-47
+    if (!res->col_types[y]) res->col_types[y] = gb_natural_type(c.kind);
+    if (c.is_const && c.kind == VK_STRING && (c.const_bits & 1)) res->const_str[0][y] = c.const_str;
+  }
+  plan.y.code = pb.code;
+  plan.y.data = pb.data;
+  plan.y.nregs = std::max(1, pb.max_reg);
+  for (const Ins& i : plan.y.code) {
+    if (i.op == OP_SOUT || i.op == OP_SMAT) return E.fail(NBG_E_UNSUPPORTED, "FETCH: an expression that builds a string");
+    if (i.op == OP_TAGS_E) tcols_read.insert(i.aux & 0xFFFF);
+  }
+  if ((int)(plan.y.code.size() + plan.y.data.size()) > MAX_PROGRAM) return E.fail(NBG_E_UNSUPPORTED, "FETCH: program too long");
+  if (plan.y.nregs > interp_max_regs())
+    return E.fail(NBG_E_UNSUPPORTED, "FETCH: expression too deep for the device register file (" +
+                                         std::to_string(plan.y.nregs) + " registers, " + std::to_string(interp_max_regs()) +
+                                         " fit the LDS)");
+  plan.tag_cols = (int)tcols_read.size();
+  // ---- 8. the passes
+  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+  plan.y.str = E.dev_strings();
+  plan.y.now_sec = (int64_t)time(nullptr);
+  plan.y.rand_seed = query_rand_seed();
+  plan.vids = E.snap.d_vids;
+  plan.nv = E.snap.nv;
+  plan.visible = E.snap.d_visible;
+  plan.tcols = E.snap.d_tcols;
+  plan.tpres = E.snap.d_tpres;
+  // (a knob of tools/fetch_probe.py alone, like NBG_SP_*: not part of the interface.  Read per call,
+  // so the probe can A/B both searches in one process; a getenv beside milliseconds of kernels)
+  if (const char* s = getenv("NBG_FETCH_SEARCH")) plan.search = !strcmp(s, "two-level") ? 2 : 0;
+  struct WsGuard {
+    Workspace* w = nullptr;
+    ~WsGuard() { if (w) ws_destroy(w); }
+  } first;
+  std::vector<std::pair<uint64_t, uint64_t>> segs;
+  Workspace* inw = nullptr;
+  if (in) {
+    auto* m = const_cast<nbg_rows*>(in);
+    m->build_segs();
+    for (auto& sg : m->segs)
+      if (sg.end > sg.begin) segs.emplace_back(sg.begin, sg.end - sg.begin);
+    inw = in->owned_ws ? in->owned_ws : in->ws;
+    if (!inw) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: the rows have no device workspace");
+  } else {   // the literal vids: ws_fetch_vertices uploads them into a temporary one-column result
+    segs.emplace_back(0, nin);
+  }
+  Workspace* ow = nullptr;
+  uint64_t n = 0;
+  if (int32_t rc = ws_fetch_vertices(inw, in ? nullptr : rq->vids, E.stream, segs, plan, &ow, &n, &E.fv_prof, &err)) return E.fail(rc, err);
+  // ---- YIELD DISTINCT (processResult's uniqResult, :159, :221-228): one row per distinct output
+  // row, through nbg_set_op's row table: the UNION DISTINCT of the result's two halves
+  if (ow && rq->distinct && n > 1) {
+    first.w = ow;
+    SoPlan sp;
+    sp.op = NBG_SET_UNION;
+    sp.distinct = 1;
+    sp.ncols = ny;
+    for (int c = 0; c < ny; ++c) sp.dbl[c] = res->kinds[0][c] == VK_DOUBLE;   // (-0.0 == 0.0, as nbg_set_op)
+    const uint64_t half = n / 2;
+    ow = nullptr;
+    if (int32_t rc = ws_set_op(first.w, first.w, E.stream, {{0, half}}, {{half, n - half}}, sp, &ow, &n, &E.so_prof, &err))
+      return E.fail(rc, err);
+  }
+  if (ow) fv_adopt(res.get(), ow, n, ny);
+  *out = res.release();
+  return NBG_OK;
+}
+
 int32_t nbg_set_path_replica(nbg_engine* h, int32_t mode) {
   if (!h || mode < 0 || mode > 1) return NBG_E_INVALID_ARGUMENT;
   Engine& E = h->e;
@@ -2979,6 +3223,8 @@ int32_t nbg_profile(nbg_engine* h, int32_t enable) {
   E.so_prof.on = mode == 1;
   if (mode) E.yr_prof = YrProf{};
   E.yr_prof.on = mode == 1;
+  if (mode) E.fv_prof = FvProf{};
+  E.fv_prof.on = mode == 1;
   // the one-pair SHORTEST contexts (device-driven chains): their launches and algorithmic bytes
   for (Engine* P : {&E, E.rep.get()}) {   // (and the FIND PATH replica's)
     if (!P) continue;
@@ -3024,6 +3270,12 @@ int32_t nbg_profile_read(const nbg_engine* h, nbg_kernel_stat* out, int32_t cap)
     out[n].launches = E.yr_prof.launches[k];
     out[n].total_ms = E.yr_prof.ms[k];
     out[n].algo_bytes = E.yr_prof.bytes[k];
+  }
+  for (int k = 0; k < FV_KINDS && n < cap; ++k, ++n) {   // nbg_fetch_vertices' kernels (fetchrows.hip)
+    out[n].name = kFvKernelNames[k];
+    out[n].launches = E.fv_prof.launches[k];
+    out[n].total_ms = E.fv_prof.ms[k];
+    out[n].algo_bytes = E.fv_prof.bytes[k];
   }
   return n;
 }

@@ -62,6 +62,7 @@ struct Engine {
   ObProf ob_prof;                       // nbg_order_by's kernels (nbg_profile mode 1)
   SoProf so_prof;                       // nbg_set_op's kernels
   YrProf yr_prof;                       // nbg_yield's kernels
+  FvProf fv_prof;                       // nbg_fetch_vertices' kernels
   // pinned host blocks of fetched GO rows (nbg_rows_fetch), reused across queries
   std::mutex pinned_mu;
   std::vector<std::pair<size_t, void*>> pinned_free;

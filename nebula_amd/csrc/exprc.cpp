@@ -696,6 +696,26 @@ struct Ctx {
     return NBG_OK;
   }
 
+  // FETCH PROP ON tag: `tag.prop` of the found vertex (FetchVerticesExecutor.cpp:199-203, the
+  // getAliasProp getter over the vertex's row).  The row kernels only evaluate vertices that carry
+  // the tag, so OP_TAGS_E's error branch is never taken.
+  int32_t leaf_fetch_tag(const Node& e, Compiled* out) {
+    const DevTag* dt;
+    int col = -1;
+    int32_t rc = e.kind == EK_ALIAS && e.alias == *env.fetch_tag ? tag_column(e, &dt, &col) : NBG_E_TAG_PROP_NOT_FOUND;
+    if (rc == NBG_E_UNSUPPORTED) return rc;
+    if (rc || col < 0) {
+      *err = "prop `" + e.alias + "." + e.prop + "' not found";
+      return NBG_E_EXECUTION_ERROR;
+    }
+    Compiled c;
+    c.kind = dt->kind[col];
+    c.reg = push();
+    emit(OP_TAGS_E, c.reg, 0, 0, (dt->index << 16) | (dt->col_base + col), 0);
+    *out = c;
+    return NBG_OK;
+  }
+
   // $$.tag.prop: VertexHolder::get over the final destinations' tag data (GoExecutor.cpp:986-1064)
   int32_t leaf_dst_tag(const Node& e, Compiled* out) {
     const DevTag* dt;
@@ -736,6 +756,7 @@ struct Ctx {
     }
     switch (e.kind) {
       case EK_ALIAS: case EK_DST: case EK_SRCID: case EK_RANK:
+        if (env.fetch_tag) return leaf_fetch_tag(e, out);
         return leaf_alias(e, out);
       case EK_TYPE: {
         int32_t et;

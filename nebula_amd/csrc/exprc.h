@@ -58,6 +58,10 @@ struct CompileEnv {
   // direct load of column aux at the lane's row: OP_COL with ExpandArgs::props = the row column
   // bases and EdgeCtx::j = the physical row (no index search as OP_INPUT's)
   bool rows = false;
+  // fetch mode (nbg_fetch_vertices, with rows): the program runs per input row whose vid was found;
+  // EdgeCtx::v = that vertex's dense id.  `tag.prop` (EK_ALIAS naming this tag; the caller has
+  // checked the alias and the prop) is OP_TAGS_E over the tag's column with ExpandArgs::gbase = 0
+  const std::string* fetch_tag = nullptr;
 };
 
 // One piece of a derived string (a STRING value built on the device: concatenation, casts to

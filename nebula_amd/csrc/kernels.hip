@@ -1167,6 +1167,145 @@ hipError_t launch_yr_emit(const YrArgs& a, int nregs, unsigned grid, hipStream_t
   return hipGetLastError();
 }
 
+// ----------------------------------------------------------------------------- k_fv_resolve / k_fv_emit
+// nbg_fetch_vertices' row kernels (driven by fetchrows.hip).  The program was compiled in
+// CompileEnv's fetch mode: `tag.prop` is OP_TAGS_E with gbase = 0 and EdgeCtx::v = the row's dense
+// vertex id, which k_fv_resolve found.  Chunks and LDS registers as k_yr_*.
+
+// the vid -> dense id join: the first entry of vids[lo, hi) not below `vid` (signed order)
+__device__ __forceinline__ uint64_t fv_lower_bound(const int64_t* __restrict__ vids, uint64_t lo, uint64_t hi, int64_t vid) {
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (vids[mid] < vid) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// per row: the vid cell, its dense id (4 bytes) and a keep byte (in d_vids, carries the tag, lives
+// in the part the storage client asks); per chunk the kept count (a plain store, as k_yr_filter).
+// TWO: FV_PIVOTS evenly sampled vids (pivot p = vids[p * nv / FV_PIVOTS]) are staged in LDS once
+// per workgroup; a lane finds its bucket there and searches only vids[bucket] in global memory.
+// The host picks TWO only on request (it measured slower than the plain search) and
+// only when nv >= 2 * FV_PIVOTS, so the pivots are distinct entries.
+template <bool TWO>
+__global__ void __launch_bounds__(BLOCK) k_fv_resolve(FvArgs f) {
+  __shared__ int64_t pivot[TWO ? FV_PIVOTS : 1];
+  __shared__ uint32_t wcnt[WAVES];
+  const YrArgs& y = f.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t nv = f.nv;
+  if (TWO) {
+    for (int p = threadIdx.x; p < FV_PIVOTS; p += BLOCK) pivot[p] = f.vids[(uint64_t)p * nv / FV_PIVOTS];
+    __syncthreads();
+  }
+  const int64_t* __restrict__ vcol = y.cols[f.vid_col];
+  for (uint32_t k = blockIdx.x; k < y.nchunks; k += gridDim.x) {
+    const uint64_t b = y.chunk[3 * k], len = y.chunk[3 * k + 1], lo = y.chunk[3 * k + 2];
+    uint32_t mine = 0;   // (wave-uniform)
+    for (uint64_t c0 = 0; c0 < len; c0 += BLOCK) {
+      const uint64_t i = c0 + threadIdx.x;
+      const bool valid = i < len;
+      bool found = false;
+      uint64_t d = 0;
+      if (valid) {
+        const int64_t vid = vcol[b + i];
+        uint64_t s0 = 0, s1 = nv;
+        if (TWO) {
+          // the last pivot not above vid (pivot[0] = vids[0]: a vid below it is nowhere)
+          int p0 = 0, p1 = FV_PIVOTS;   // pivot[p0] <= vid < pivot[p1] once vid >= pivot[0]
+          while (p1 - p0 > 1) {
+            const int pm = (p0 + p1) >> 1;
+            if (pivot[pm] <= vid) p0 = pm;
+            else p1 = pm;
+          }
+          s0 = (uint64_t)p0 * nv / FV_PIVOTS;
+          s1 = p1 == FV_PIVOTS ? nv : (uint64_t)p1 * nv / FV_PIVOTS;
+        }
+        d = fv_lower_bound(f.vids, s0, s1, vid);
+        found = d < nv && f.vids[d] == vid && f.pres[d] && (!f.visible || f.visible[d]);
+        f.dense[lo + i] = (uint32_t)(found ? d : 0);
+        y.keep[lo + i] = found;
+      }
+      mine += (uint32_t)__popcll(__ballot(found));
+    }
+    if (lane == 0) wcnt[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t t = 0;
+      for (int w = 0; w < WAVES; ++w) t += wcnt[w];
+      y.ccount[k] = t;
+    }
+    __syncthreads();   // (wcnt is rewritten for the next chunk)
+  }
+}
+
+// k_yr_emit over the found rows with EdgeCtx::v = the row's dense id; a column is a register, the
+// constant (-1), or tag column -2 - r of the found vertex as it is
+__global__ void __launch_bounds__(BLOCK) k_fv_emit(FvArgs f) {
+  extern __shared__ int64_t regs[];   // [nregs][BLOCK]
+  constexpr int STEPS = (int)(OB_CHUNK / BLOCK);
+  __shared__ uint32_t woff[STEPS * WAVES];
+  const YrArgs& y = f.y;
+  ExpandArgs a = yr_expand_args(y);
+  a.tcols = f.tcols;
+  a.tpres = f.tpres;
+  a.vids = f.vids;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  bool any_err = false;
+  for (uint32_t k = blockIdx.x; k < y.nchunks; k += gridDim.x) {
+    const uint64_t b = y.chunk[3 * k], len = y.chunk[3 * k + 1], lo = y.chunk[3 * k + 2];   // len <= OB_CHUNK
+    const int steps = (int)((len < OB_CHUNK ? len : OB_CHUNK) + BLOCK - 1) / BLOCK;         // <= STEPS
+    for (int s = 0; s < steps; ++s) {
+      const uint64_t i = (uint64_t)s * BLOCK + threadIdx.x;
+      const bool take = i < len && y.keep[lo + (i < len ? i : 0)];
+      const unsigned long long bal = __ballot(take);
+      if (lane == 0) woff[s * WAVES + wave] = (uint32_t)__popcll(bal);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t total = 0;
+      for (int j = 0; j < steps * WAVES; ++j) {
+        const uint32_t c = woff[j];
+        woff[j] = total;
+        total += c;
+      }
+    }
+    __syncthreads();
+    const uint64_t base = y.cbase[k];
+    for (int s = 0; s < steps; ++s) {
+      const uint64_t i = (uint64_t)s * BLOCK + threadIdx.x;
+      const bool take = i < len && y.keep[lo + (i < len ? i : 0)];
+      const unsigned long long bal = __ballot(take);
+      if (!bal) continue;   // (wave-uniform)
+      const uint64_t slot = base + woff[s * WAVES + wave] + lane_rank(bal);
+      bool yerr = false;
+      uint32_t tbits = 0;
+      const EdgeCtx c{b + (take ? i : 0), take ? f.dense[lo + i] : 0u};
+      if (y.code_len > 0)   // (bare props and constants have no YIELD code)
+        run_program(y.prog, y.prog + y.code_len, 0, y.code_len, c, a, regs, take, yerr, tbits);
+      any_err = any_err || (take && yerr);
+      if (take && slot < y.cap)
+        for (int col = 0; col < y.ncols; ++col) {
+          const int r = y.yield_reg[col];
+          y.out[col][slot] = r >= 0 ? regs[r * BLOCK + threadIdx.x] : r == -1 ? y.yield_const[col] : f.tcols[-2 - r][c.v];
+        }
+    }
+    __syncthreads();   // (woff is rewritten for the next chunk)
+  }
+  if (__ballot(any_err) && lane == 0) atomicOr(y.err, 1ull);
+}
+
+hipError_t launch_fv_resolve(const FvArgs& a, unsigned grid, hipStream_t s) {
+  if (a.two_level) hipLaunchKernelGGL(k_fv_resolve<true>, dim3(grid), dim3(BLOCK), 0, s, a);
+  else hipLaunchKernelGGL(k_fv_resolve<false>, dim3(grid), dim3(BLOCK), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_fv_emit(const FvArgs& a, int nregs, unsigned grid, hipStream_t s) {
+  hipLaunchKernelGGL(k_fv_emit, dim3(grid), dim3(BLOCK), (size_t)nregs * BLOCK * 8, s, a);
+  return hipGetLastError();
+}
+
 // ----------------------------------------------------------------------------- k_expand
 // FINALF: the final step with a FastProg program (no interpreter: fewer registers, 8 waves/SIMD)
 // FINALD: FINALF whose YIELDs are only _dst / constants; a tile's rows are stored after the NEXT

@@ -491,6 +491,16 @@ int32_t Engine::upload_tags() {
     std::vector<uint8_t> pres(local, 0);
     for (uint64_t d = 0; d < nv; ++d) pres[d] = dt.h_present[d] != 0;
     bool ok = up((void**)&dt.present, pres.data(), space);
+    // nbg_fetch_vertices finds decoded records only (collectProps skips a bad value,
+    // QueryBaseProcessor.inl:323-326); OP_TAGS / OP_TAGD keep reading `present`.  Single engine
+    // only: h_present is this rank's, so on a partitioned engine the test below would differ
+    // between ranks while up() is a collective; nbg_fetch_vertices refuses such an engine anyway
+    dt.decoded = dt.present;
+    if (ok && !partitioned() && std::find(dt.h_present.begin(), dt.h_present.end(), (uint8_t)2) != dt.h_present.end()) {
+      for (uint64_t d = 0; d < nv; ++d) pres[d] = dt.h_present[d] == 1;
+      dt.decoded = nullptr;
+      ok = up((void**)&dt.decoded, pres.data(), space);
+    }
     dt.cols.assign(dt.h_cols.size(), nullptr);
     std::vector<int64_t> buf(local, 0);
     for (size_t c = 0; ok && c < dt.h_cols.size(); ++c) {

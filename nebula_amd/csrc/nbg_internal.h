@@ -109,6 +109,9 @@ struct DevTag {
   int index = 0;                // position in Snapshot::d_tpres
   int col_base = 0;             // first column in Snapshot::d_tcols
   uint8_t* present = nullptr;   // [tag_space] the vertex has a record of this tag
+  uint8_t* decoded = nullptr;   // [tag_space] ... and it decoded (h_present == 1): what FETCH PROP finds.
+                                // `present` itself unless some record of the tag is undecodable
+                                // (and always on a partitioned engine, which has no FETCH)
   std::vector<int64_t*> cols;   // [ncols][tag_space] latest-schema columns
   std::vector<VKind> kind;
   // host copies over this engine's local dense ids (GetNeighbors tag rows are built on the host)
@@ -875,7 +878,13 @@ struct YrArgs {
   int64_t now_sec;
   uint64_t rand_seed;
 };
+// what the host reads back in one copy: the kept rows and the evaluation errors
+struct YrState {
+  unsigned long long total, err;
+};
 hipError_t launch_yr_filter(const YrArgs& a, int nregs, unsigned grid, hipStream_t s);
+// k_yr_scan: base[k] = sum of count[0..k), st->total = the sum (one workgroup)
+hipError_t launch_yr_scan(const uint32_t* count, uint32_t n, uint32_t* base, YrState* st, hipStream_t s);
 hipError_t launch_yr_emit(const YrArgs& a, int nregs, unsigned grid, hipStream_t s);
 // Filters and projects the rows of `inw` listed by segs (first row, rows) into a fresh rows-only
 // workspace on `stream` (*outw; nullptr when no row passes) of *rows rows, in the input's order.
@@ -883,6 +892,53 @@ hipError_t launch_yr_emit(const YrArgs& a, int nregs, unsigned grid, hipStream_t
 // NBG_E_EXECUTION_ERROR (an evaluation error), NBG_E_OUT_OF_MEMORY or NBG_E_DEVICE.
 int32_t ws_yield_rows(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
                       const YrPlan& plan, Workspace** outw, uint64_t* rows, YrProf* prof, std::string* err);
+
+// ---- FETCH PROP ON <tag> over device rows (fetchrows.hip; FetchVerticesExecutor.cpp:19-311).  The
+// vid column is joined to the dense vertex ids (k_fv_resolve), the found rows are ranked
+// (k_yr_scan) and the YIELDs are evaluated with EdgeCtx::v = the row's dense id (k_fv_emit), so
+// `tag.prop` is OP_TAGS_E over the tag columns (CompileEnv::fetch_tag).
+constexpr int FV_PIVOTS = 2048;     // two-level search (measured, not shipped): sampled vids staged in LDS (16 KB)
+struct FvPlan {
+  YrPlan y;                         // no WHERE; yield_reg -2 - c: tag column c (Snapshot::d_tcols) as it is
+  int vid_col = 0;                  // the input column holding the vids
+  const uint8_t* pres = nullptr;    // DevTag::decoded of the tag: the vertex carries a decoded record
+  int tag_cols = 0;                // distinct tag columns the YIELDs read (profiling bytes)
+  const int64_t* vids = nullptr;    // Snapshot::d_vids / nv / d_visible / d_tcols / d_tpres
+  uint64_t nv = 0;
+  const uint8_t* visible = nullptr;
+  const int64_t* const* tcols = nullptr;
+  const uint8_t* const* tpres = nullptr;
+  int search = 0;                   // 0 / 1: the plain binary search (shipped); 2: two-level from 2 * FV_PIVOTS vertices
+};
+enum FvKernel { FV_K_RESOLVE = 0, FV_K_EMIT, FV_KINDS };   // (the scan between them is k_yr_scan, untimed here)
+extern const char* const kFvKernelNames[FV_KINDS];
+struct FvProf {
+  bool on = false;
+  uint64_t launches[FV_KINDS] = {};
+  double ms[FV_KINDS] = {};
+  double bytes[FV_KINDS] = {};
+};
+struct FvArgs {
+  YrArgs y;                         // keep / ccount / cbase always set; cols: the input's column bases
+  int vid_col;
+  const int64_t* vids;
+  uint64_t nv;
+  const uint8_t* pres;              // the tag's decoded-record bytes (DevTag::decoded)
+  const uint8_t* visible;           // nullptr: every vertex is visible
+  uint32_t* dense;                  // one dense id per logical row (read only where keep is set)
+  const int64_t* const* tcols;
+  const uint8_t* const* tpres;
+  int two_level;
+};
+hipError_t launch_fv_resolve(const FvArgs& a, unsigned grid, hipStream_t s);
+hipError_t launch_fv_emit(const FvArgs& a, int nregs, unsigned grid, hipStream_t s);
+// Joins the vid column of the rows of `inw` listed by segs (inw == nullptr: the segs[0].second
+// vids at `host_vids`, uploaded into a temporary one-column result) to the vertices and projects the found
+// rows into a fresh rows-only workspace on `stream` (*outw; nullptr when no vid is found) of *rows
+// rows, in the input's order.  Synchronous; every scratch allocation is released before it
+// returns.  NBG_OK, NBG_E_EXECUTION_ERROR (an evaluation error), NBG_E_OUT_OF_MEMORY or NBG_E_DEVICE.
+int32_t ws_fetch_vertices(Workspace* inw, const int64_t* host_vids, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
+                          const FvPlan& plan, Workspace** outw, uint64_t* rows, FvProf* prof, std::string* err);
 
 // Query pipeline (all asynchronous on the workspace stream until ws_end_query):
 hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, const std::vector<TypeProgram>* progs,

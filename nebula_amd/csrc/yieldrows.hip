@@ -26,11 +26,6 @@ const char* const kYrKernelNames[YR_KINDS] = {"k_yr_filter", "k_yr_scan", "k_yr_
 
 namespace {
 
-// what the host reads back in one copy: the kept rows and the evaluation errors
-struct YrState {
-  unsigned long long total, err;
-};
-
 // base[k] = sum of count[0..k), st->total = the sum of all; each thread scans a contiguous slice
 __global__ void __launch_bounds__(BLOCK) k_yr_scan(const uint32_t* __restrict__ count, uint32_t n,
                                                    uint32_t* __restrict__ base, YrState* __restrict__ st) {
@@ -51,6 +46,11 @@ __global__ void __launch_bounds__(BLOCK) k_yr_scan(const uint32_t* __restrict__ 
 }
 
 }  // namespace
+
+hipError_t launch_yr_scan(const uint32_t* count, uint32_t n, uint32_t* base, YrState* st, hipStream_t s) {
+  hipLaunchKernelGGL(k_yr_scan, dim3(1), dim3(BLOCK), 0, s, count, n, base, st);
+  return hipGetLastError();
+}
 
 int32_t ws_yield_rows(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
                       const YrPlan& plan, Workspace** outw, uint64_t* rows, YrProf* prof, std::string* err) {

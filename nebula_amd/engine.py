@@ -278,8 +278,13 @@ class Engine:
         self._check(self.lib.nbg_profile(self.h, int(enable)), "profile")
 
     def profile_read(self):
-        arr = (L.nbg_kernel_stat * 64)()
-        n = self.lib.nbg_profile_read(self.h, arr, 64)
+        cap = 64
+        while True:                        # (the call fills at most `cap` entries: a full buffer may be a cut one)
+            arr = (L.nbg_kernel_stat * cap)()
+            n = self.lib.nbg_profile_read(self.h, arr, cap)
+            if n < cap:
+                break
+            cap *= 2
         return {arr[i].name.decode(): {"launches": arr[i].launches, "ms": arr[i].total_ms,
                                        "algo_bytes": arr[i].algo_bytes} for i in range(n)}
 
@@ -450,6 +455,31 @@ class Engine:
         req = L.nbg_yield_request(names, wptr, len(wbuf), ptrs, lens, fptr, len(bufs))
         out = C.c_void_p()
         self._check(self.lib.nbg_yield(self.h, rows.h, C.byref(req), C.byref(out)), "yield_rows")
+        return DeviceRows(self, out)
+
+    def fetch_vertices(self, rows_or_vids, input_names, vid_col, tag_id, yields=(), distinct=False) -> DeviceRows:
+        """nbg_fetch_vertices: ``| FETCH PROP ON <tag> $-.vid_col YIELD [DISTINCT] yields`` over a
+        device-resident result, or ``FETCH PROP ON <tag> vids`` when ``rows_or_vids`` is a
+        sequence of vids (``input_names`` / ``vid_col`` are then unused).  ``yields`` holds
+        Expression::encode bytes per YIELD column; none means every column of the tag's latest
+        schema.  The result is a new DeviceRows with one row per input row whose vid carries the
+        tag, in the input's row order; the input stays valid and unchanged."""
+        bufs = [np.frombuffer(bytes(b), np.uint8).copy() for b in yields]
+        ptrs = (C.POINTER(C.c_uint8) * max(1, len(bufs)))(*[b.ctypes.data_as(C.POINTER(C.c_uint8)) for b in bufs])
+        lens = (C.c_uint32 * max(1, len(bufs)))(*[len(b) for b in bufs])
+        if isinstance(rows_or_vids, DeviceRows):
+            names = (C.c_char_p * max(1, len(input_names)))(*[n.encode() for n in input_names])
+            req = L.nbg_fetch_request(names, vid_col.encode(), None, 0, int(tag_id), ptrs, lens, len(bufs),
+                                      int(bool(distinct)))
+            handle = rows_or_vids.h
+        else:
+            vids = np.ascontiguousarray(np.asarray(list(rows_or_vids), dtype=np.int64))
+            vptr = vids.ctypes.data_as(C.POINTER(C.c_int64)) if len(vids) else None
+            req = L.nbg_fetch_request(None, None, vptr, len(vids), int(tag_id), ptrs, lens, len(bufs),
+                                      int(bool(distinct)))
+            handle = None
+        out = C.c_void_p()
+        self._check(self.lib.nbg_fetch_vertices(self.h, handle, C.byref(req), C.byref(out)), "fetch_vertices")
         return DeviceRows(self, out)
 
     def default_columns(self, etypes, over_all=False):
