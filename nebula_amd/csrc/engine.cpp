@@ -19,12 +19,13 @@
 #include <unordered_map>
 
 #include "engine.h"
+#include "nbg_rows.h"
 
 static_assert(NBG_MAX_YIELDS == nbg::MAX_YIELDS && NBG_MAX_OVER == nbg::MAX_TYPES_Q,
               "include/nbg.h device limits match the engine's");
 
 // a fresh seed for each query's rand32 / rand64 stream
-static uint64_t query_rand_seed() {
+uint64_t nbg::query_rand_seed() {
   static std::atomic<uint64_t> ctr{(uint64_t)std::chrono::steady_clock::now().time_since_epoch().count() * 0x9e3779b97f4a7c15ull};
   return ctr.fetch_add(0x9e3779b97f4a7c15ull, std::memory_order_relaxed);
 }
@@ -140,76 +141,6 @@ uint32_t Engine::dense(int64_t vid) const {
 
 }  // namespace nbg
 
-// ============================================================================= result objects
-struct nbg_rows {
-  struct Seg {
-    uint64_t begin = 0, end = 0;
-    int type = 0;                          // index into kinds / const_str (OVER position)
-  };
-  std::vector<std::vector<VKind>> kinds;              // per OVER type: value kind of each column
-  std::vector<std::vector<std::string>> const_str;    // per OVER type: string constants absent from the dictionary
-  Engine* eng = nullptr;
-  Workspace* ws = nullptr;               // the workspace holding the rows (device results)
-  Workspace* owned_ws = nullptr;         // set when the engine handed that workspace over (ws_release)
-  int ncols = 0;
-  uint64_t count = 0;
-  bool on_device = false;
-  bool fetched = false;
-  std::vector<int64_t*> dcols;           // column bases; rows live in segs (disjoint regions)
-  // host copy (nbg_rows_fetch): column c at hbits + c * count, in pinned memory from the engine's
-  // pool (DMA straight from the packed device copy, no staging and no zero-fill)
-  int64_t* hbits = nullptr;
-  size_t hbytes = 0;
-  std::vector<std::vector<uint8_t>> tags;   // per-cell kinds, built on the first nbg_rows_col_tags
-  std::vector<std::string> strings;
-  std::unordered_map<int64_t, std::string> derived;   // STR_DERIVED codes -> their text
-  std::vector<Seg> segs;                 // built on first use from the per-workgroup counts
-  struct TypeBlocks {
-    uint64_t region = 0, blk_cap = 0;
-    std::vector<uint32_t> counts;        // rows per workgroup of the final expansion
-  };
-  std::vector<TypeBlocks> blocks;
-  bool segs_built = false;
-  void build_segs() {
-    if (segs_built) return;
-    segs_built = true;
-    size_t n = 0;
-    for (auto& tb : blocks)
-      for (uint32_t c : tb.counts) n += c != 0;
-    segs.reserve(n);
-    for (size_t i = 0; i < blocks.size(); ++i) {
-      const TypeBlocks& tb = blocks[i];
-      for (size_t b = 0; b < tb.counts.size(); ++b) {
-        if (!tb.counts[b]) continue;
-        Seg seg;
-        seg.begin = tb.region + (uint64_t)b * tb.blk_cap;
-        seg.end = seg.begin + tb.counts[b];
-        seg.type = (int)i;
-        segs.push_back(seg);
-      }
-    }
-  }
-  int64_t* col(int c) const { return hbits + (uint64_t)c * count; }
-  // the kind of column c when every OVER type gives it the same one (else -1: per-cell tags)
-  int col_kind(int c) const {
-    int k = -1;
-    for (auto& kv : kinds) {
-      if ((int)kv.size() <= c) continue;
-      if (k < 0) k = kv[c];
-      else if (k != kv[c]) return -1;
-    }
-    return k < 0 ? VK_INT : k;
-  }
-  uint64_t scanned = 0;
-  std::vector<uint64_t> step_frontier, step_edges;
-  // the result schema (GoExecutor::setupInterimResult): NBG_T_* per column, what RowWriter wrote
-  // per (OVER type, column), and the read-back hazards it implies (see go_prepare)
-  std::vector<int32_t> col_types;
-  std::vector<std::vector<uint8_t>> wclass;
-  bool small_ok = false;     // the end-of-query kernel may have packed these rows (ws_host_small_rows)
-  bool misaligned = false;   // some column's written bytes differ in length from what its reader takes
-  bool float_col = false;    // a FLOAT column: InterimResult::getRows fails on it
-};
 
 namespace nbg {
 
@@ -262,10 +193,6 @@ namespace {
 // The rows of a result into host memory: the device packs the segments into contiguous columns
 // and DMAs them into a pinned block (nbg.h nbg_rows_fetch).  Only STRING columns are touched per
 // cell on the host (dictionary code -> the result's string table).
-// RowWriter's written form of one value (RowWriter.cpp:103-186, RowWriter.inl:9-33): the value
-// itself (ID), or the default it falls back to for an incompatible column type — varint 0 / a
-// false byte (ONE zero byte) or a 0.0 double (EIGHT zero bytes).
-enum WClass : uint8_t { W_ID = 0, W_ONE = 1, W_EIGHT = 2 };
 WClass written_class(VKind k, int32_t t) {
   switch (k) {
     case VK_INT: return (t == NBG_T_INT || t == NBG_T_TIMESTAMP || t == NBG_T_VID) ? W_ID : W_ONE;
@@ -677,11 +604,7 @@ static int32_t go_prepare(Engine& E, const nbg_go_request* rq, nbg_go_stmt** out
   std::map<std::string, std::set<std::string>> named;
   alias_props(where.get(), named);
   for (auto& y : yields) alias_props(y.get(), named);
-  if (E.max_dict_len_of != E.snap.strings.size()) {   // (cached: the dictionary is fixed after finalize)
-    E.max_dict_len = 0;
-    for (const std::string& x : E.snap.strings) E.max_dict_len = std::max<uint64_t>(E.max_dict_len, x.size());
-    E.max_dict_len_of = E.snap.strings.size();
-  }
+  E.refresh_max_dict_len();
   for (int32_t t : over) {
     auto it = E.snap.types.find(t);
     CompileEnv env{t, &over, &E.edges, &E.snap.strings,
@@ -2109,1092 +2032,6 @@ void nbg_rows_free(nbg_rows* r) {
   delete r;
 }
 
-// ============================================================================= GROUP BY
-// GroupByExecutor (src/graph/GroupByExecutor.cpp:44-178 the checks, :226-322 the grouping,
-// :355-391 the result schema) over a device-resident result; the kernels are in groupby.hip.
-namespace {
-
-bool gb_only_constants(const Node& n) {   // no prop, input or variable reference anywhere
-  switch (n.kind) {
-    case EK_PRIMARY: case EK_FUNC: case EK_UNARY: case EK_CAST: case EK_ARITH: case EK_REL: case EK_LOGIC: break;
-    default: return false;
-  }
-  for (auto& k : n.kids)
-    if (!k || !gb_only_constants(*k)) return false;
-  return true;
-}
-
-bool gb_is_agg_name(std::string f) {
-  for (char& ch : f) ch = (char)toupper((unsigned char)ch);
-  for (const char* a : {"COUNT", "COUNT_DISTINCT", "SUM", "AVG", "MAX", "MIN", "STD", "BIT_AND", "BIT_OR", "BIT_XOR"})
-    if (f == a) return true;
-  return false;
-}
-
-// PrimaryExpression::toString of a constant (what a bare name in GROUP BY is compared to)
-std::string gb_primary_string(const Node& n) {
-  if (n.kind != EK_PRIMARY) return std::string("\x01");   // (never an alias)
-  switch (n.prim.index()) {
-    case 0: return std::to_string(std::get<0>(n.prim));
-    case 1: return std::to_string(std::get<1>(n.prim));
-    case 2: return std::get<2>(n.prim) ? "true" : "false";
-    default: return std::get<3>(n.prim);
-  }
-}
-
-int32_t gb_natural_type(VKind k) {
-  return k == VK_DOUBLE ? NBG_T_DOUBLE : k == VK_BOOL ? NBG_T_BOOL : k == VK_STRING ? NBG_T_STRING : NBG_T_INT;
-}
-
-struct GbValue {          // a YIELD operand: an input column or a constant
-  int col = -1;
-  VKind kind = VK_INT;
-  int32_t type = NBG_T_INT;
-  int64_t bits = 0;       // constant payload (strings: the dictionary code)
-  std::string text;       // constant string
-};
-
-nbg_rows* gb_new_rows(Engine& E, int ncols) {
-  auto* r = new nbg_rows();
-  r->eng = &E;
-  r->ncols = ncols;
-  r->on_device = true;
-  r->kinds.emplace_back(ncols, VK_INT);
-  r->const_str.emplace_back(ncols, std::string());
-  r->col_types.assign(ncols, NBG_T_INT);
-  r->wclass.emplace_back(ncols, (uint8_t)W_ID);
-  return r;
-}
-
-}  // namespace
-
-int32_t nbg_group_by(nbg_engine* h, const nbg_rows* in, const nbg_group_request* rq, nbg_rows** out) {
-  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
-  *out = nullptr;
-  Engine& E = h->e;
-  std::lock_guard<std::mutex> lg(E.mu);
-  if (in->eng != &E) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: the rows belong to another engine");
-  if (!in->on_device) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: the rows are host-only (not a device result)");
-  if (E.partitioned())
-    return E.fail(NBG_E_UNSUPPORTED, "GROUP BY on a partitioned engine (its rows live on several ranks)");
-  const int ng = rq->num_groups, ny = rq->num_yields;
-  if (!in->count) {   // GroupByExecutor::execute returns before checkAll: no check, no rows
-    *out = gb_new_rows(E, std::max(0, std::min(ny, (int)MAX_YIELDS)));
-    return NBG_OK;
-  }
-  if ((ng > 0 && (!rq->group_exprs || !rq->group_lens)) ||
-      (ny > 0 && (!rq->yield_exprs || !rq->yield_lens || !rq->yield_funs)) || !rq->input_names)
-    return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: null argument");
-  if (ng > MAX_YIELDS || ny > MAX_YIELDS)
-    return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: more than NBG_MAX_YIELDS group or yield columns");
-  std::vector<std::string> names;
-  for (int c = 0; c < in->ncols; ++c) {
-    if (!rq->input_names[c]) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: null input column name");
-    names.emplace_back(rq->input_names[c]);
-  }
-  auto find_col = [&](const std::string& n) {
-    auto it = std::find(names.begin(), names.end(), n);
-    return it == names.end() ? -1 : (int)(it - names.begin());
-  };
-  auto decode = [&](const uint8_t* p, uint32_t n, std::unique_ptr<Node>* node) -> int32_t {
-    std::string err;
-    if (!p || !n) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: an empty expression");
-    *node = decode_expr(p, n, &err);
-    return *node ? NBG_OK : E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: " + err);
-  };
-  // ---- prepareYield / prepareGroup / checkAll
-  if (ny <= 0) return E.fail(NBG_E_SYNTAX_ERROR, "Yield cols is empty");
-  std::vector<std::unique_ptr<Node>> ynodes(ny), gnodes(std::max(ng, 0));
-  std::map<std::string, int> aliases;   // alias -> the first `$-.x AS alias` yield
-  for (int y = 0; y < ny; ++y) {
-    if (int32_t rc = decode(rq->yield_exprs[y], rq->yield_lens[y], &ynodes[y])) return rc;
-    const int32_t f = rq->yield_funs[y];
-    if (f < NBG_AGG_NONE || f > NBG_AGG_BIT_XOR) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: unknown function");
-    const Node& n = *ynodes[y];
-    const bool star = n.kind == EK_PRIMARY && n.prim.index() == 3 && std::get<3>(n.prim) == "*";
-    if (star && f != NBG_AGG_COUNT && f != NBG_AGG_COUNT_DISTINCT) return E.fail(NBG_E_SYNTAX_ERROR, "Syntax error: near `*'");
-    const char* al = rq->yield_aliases ? rq->yield_aliases[y] : nullptr;
-    if (al && n.kind == EK_INPUT) aliases.emplace(al, y);
-  }
-  if (ng <= 0) return E.fail(NBG_E_SYNTAX_ERROR, "Group cols is empty");
-  std::set<int> key_set;          // the `$-` group keys (input columns)
-  std::vector<int> key_cols;
-  for (int g = 0; g < ng; ++g) {
-    if (int32_t rc = decode(rq->group_exprs[g], rq->group_lens[g], &gnodes[g])) return rc;
-    const Node& n = *gnodes[g];
-    if (n.kind == EK_FUNC && gb_is_agg_name(n.alias))
-      return E.fail(NBG_E_SYNTAX_ERROR, "Use invalid group function `" + n.alias + "'");
-  }
-  for (int g = 0; g < ng; ++g) {
-    const Node& n = *gnodes[g];
-    if (n.kind == EK_INPUT) {
-      const int c = find_col(n.prop);
-      if (c < 0) return E.fail(NBG_E_SYNTAX_ERROR, "Group `" + n.prop + "' isn't in output fields");
-      if (key_set.insert(c).second) key_cols.push_back(c);
-      continue;
-    }
-    if (n.kind == EK_FUNC) continue;   // (constant-folded below)
-    const std::string gname = gb_primary_string(n);
-    auto a = aliases.find(gname);
-    if (a == aliases.end()) return E.fail(NBG_E_SYNTAX_ERROR, "Group `" + gname + "' isn't in output fields");
-    const int c = find_col(ynodes[a->second]->prop);   // (absent: the yield check below answers)
-    if (c >= 0 && key_set.insert(c).second) key_cols.push_back(c);
-  }
-  for (int y = 0; y < ny; ++y) {
-    const Node& n = *ynodes[y];
-    if (n.kind == EK_INPUT) {
-      const int c = find_col(n.prop);
-      if (c < 0) return E.fail(NBG_E_SYNTAX_ERROR, "Yield `" + n.prop + "' isn't in output fields");
-      if (rq->yield_funs[y] == NBG_AGG_NONE && !key_set.count(c))
-        return E.fail(NBG_E_SYNTAX_ERROR, "Yield `" + n.prop + "' isn't in group fields");
-    } else if (n.kind == EK_VAR) {
-      return E.fail(NBG_E_SYNTAX_ERROR, "Can't support variableExpression");
-    }
-  }
-  // ---- device scope
-  if (in->misaligned || in->float_col)
-    return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: the input's row schema re-reads its columns (misaligned or FLOAT)");
-  static const std::vector<int32_t> no_over;
-  CompileEnv cenv{};
-  cenv.etype = 0;
-  cenv.over = &no_over;
-  cenv.edges = &E.edges;
-  cenv.strings = &E.snap.strings;
-  cenv.tags = &E.tags;
-  auto constant = [&](const Node& n, GbValue* v) -> int32_t {
-    if (!gb_only_constants(n)) return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: an expression that is neither `$-.col' nor constant");
-    ProgramBuilder pb;
-    Compiled c;
-    std::string err;
-    const int32_t rc = compile_expr(n, cenv, pb, &c, &err, true);
-    if (rc) return E.fail(rc, "GROUP BY: " + err);
-    if (c.always_error) return E.fail(NBG_E_EXECUTION_ERROR, "GROUP BY: a constant expression fails to evaluate");
-    if (!c.is_const || c.derived) return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: an expression that is not constant");
-    v->col = -1;
-    v->kind = c.kind;
-    v->type = gb_natural_type(c.kind);
-    v->bits = c.const_bits;
-    v->text = c.const_str;
-    return NBG_OK;
-  };
-  auto column = [&](int c, GbValue* v) -> int32_t {
-    if (in->col_kind(c) < 0) return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: column `" + names[c] + "' mixes value kinds");
-    v->col = c;
-    v->kind = (VKind)in->col_kind(c);
-    v->type = c < (int)in->col_types.size() && in->col_types[c] ? in->col_types[c] : gb_natural_type(v->kind);
-    return NBG_OK;
-  };
-  // a string column the result carries over: what spells its codes outside the dictionary
-  auto column_const_str = [&](int c, std::string* s) -> int32_t {
-    bool have = false;
-    for (auto& cs : in->const_str) {
-      if ((int)cs.size() <= c) continue;
-      if (have && *s != cs[c])
-        return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: column `" + names[c] + "' spells different constants per OVER type");
-      *s = cs[c];
-      have = true;
-    }
-    return NBG_OK;
-  };
-  for (int g = 0; g < ng; ++g) {   // a function-call key must fold: it adds nothing to the identity
-    if (gnodes[g]->kind != EK_FUNC) continue;
-    GbValue v;
-    if (int32_t rc = constant(*gnodes[g], &v)) return rc;
-  }
-  GbPlan plan;
-  plan.nkeys = (int)key_cols.size();
-  for (int k = 0; k < plan.nkeys; ++k) {
-    GbValue v;
-    if (int32_t rc = column(key_cols[k], &v)) return rc;
-    plan.key_col[k] = (int8_t)key_cols[k];
-    plan.key_dbl[k] = v.kind == VK_DOUBLE;
-  }
-  plan.acc[0] = GbAcc{GB_COUNT, 0, -1, 0, 0};
-  plan.nacc = 1;
-  plan.nout = ny;
-  std::unique_ptr<nbg_rows> res(gb_new_rows(E, ny));
-  auto slot = [&](GbOp op, const GbValue& v, int ref) {
-    plan.acc[plan.nacc] = GbAcc{(uint8_t)op, (uint8_t)(v.kind == VK_DOUBLE), (int8_t)v.col, (uint8_t)ref, v.bits};
-    return plan.nacc++;
-  };
-  for (int y = 0; y < ny; ++y) {
-    GbValue v;
-    const Node& n = *ynodes[y];
-    if (n.kind == EK_INPUT) {
-      if (int32_t rc = column(find_col(n.prop), &v)) return rc;
-    } else if (int32_t rc = constant(n, &v)) {
-      return rc;
-    }
-    GbOut& o = plan.out[y];
-    VKind okind = VK_INT;
-    int32_t otype = NBG_T_INT;
-    auto emit_const = [&](VKind k, int32_t t, int64_t bits) {
-      o = GbOut{GE_CONST, -1, 0, bits};
-      okind = k;
-      otype = t;
-    };
-    const bool int_like = v.type == NBG_T_INT || v.type == NBG_T_VID || v.type == NBG_T_TIMESTAMP;
-    const bool is_dbl = v.type == NBG_T_DOUBLE;
-    const double zero = 0.0;
-    int64_t zero_bits;
-    memcpy(&zero_bits, &zero, 8);
-    switch (rq->yield_funs[y]) {
-      case NBG_AGG_NONE:   // Group::apply keeps the row's value: a key cell or the constant
-        if (v.col >= 0) {
-          o = GbOut{GE_KEY, (int8_t)v.col, 0, 0};
-          okind = v.kind;
-          otype = v.type;
-          if (v.kind == VK_STRING)
-            if (int32_t rc = column_const_str(v.col, &res->const_str[0][y])) return rc;
-        } else {
-          emit_const(v.kind, v.type, v.bits);
-          res->const_str[0][y] = v.text;
-        }
-        break;
-      case NBG_AGG_COUNT:
-        o = GbOut{GE_SLOT, -1, 0, 0};
-        break;
-      case NBG_AGG_COUNT_DISTINCT:
-        if (v.col < 0) emit_const(VK_INT, NBG_T_INT, 1);
-        else o = GbOut{GE_SLOT, -1, (uint8_t)slot(GB_DISTINCT, v, 0), 0};
-        break;
-      case NBG_AGG_SUM:
-        if (int_like) {
-          o = GbOut{GE_SLOT, -1, (uint8_t)slot(GB_SUM_I, v, 0), 0};
-          otype = v.type;
-        } else if (is_dbl) {
-          o = GbOut{GE_SLOT, -1, (uint8_t)slot(GB_SUM_D, v, 0), 0};
-          okind = VK_DOUBLE;
-          otype = NBG_T_DOUBLE;
-        } else {
-          emit_const(VK_INT, NBG_T_INT, 0);
-        }
-        break;
-      case NBG_AGG_AVG:
-        okind = VK_DOUBLE;
-        otype = NBG_T_DOUBLE;
-        if (v.type == NBG_T_VID || v.type == NBG_T_TIMESTAMP)
-          return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: AVG over a VID or TIMESTAMP column");
-        if (int_like) o = GbOut{GE_AVG_I, -1, (uint8_t)slot(GB_SUM_I, v, 0), 0};
-        else if (is_dbl) o = GbOut{GE_AVG_D, -1, (uint8_t)slot(GB_SUM_D, v, 0), 0};
-        else emit_const(VK_DOUBLE, NBG_T_DOUBLE, zero_bits);
-        break;
-      case NBG_AGG_MAX: case NBG_AGG_MIN: {
-        okind = v.kind;
-        otype = v.type;
-        if (v.col < 0) {
-          emit_const(v.kind, v.type, v.bits);
-          res->const_str[0][y] = v.text;
-          break;
-        }
-        if (v.kind == VK_STRING) {
-          bool outside = !in->derived.empty();
-          for (auto& cs : in->const_str) outside = outside || ((int)cs.size() > v.col && !cs[v.col].empty());
-          if (outside)
-            return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: MAX/MIN over a string column that can hold strings outside the dictionary");
-        }
-        const GbOp op = rq->yield_funs[y] == NBG_AGG_MAX ? GB_MAX : GB_MIN;
-        o = GbOut{(uint8_t)(v.kind == VK_DOUBLE ? GE_ORD_D : GE_ORD_I), -1, (uint8_t)slot(op, v, 0), 0};
-        break;
-      }
-      case NBG_AGG_STD:
-        if (v.type == NBG_T_INT || is_dbl) {
-          const int s = slot(is_dbl ? GB_SUM_D : GB_SUM_I, v, 0);
-          o = GbOut{GE_STD, -1, (uint8_t)slot(GB_SQ, v, s), 0};
-          okind = VK_DOUBLE;
-          otype = NBG_T_DOUBLE;
-        } else {
-          emit_const(VK_INT, NBG_T_INT, 0);
-        }
-        break;
-      default: {   // BIT_AND / BIT_OR / BIT_XOR: INT values only
-        if (v.type != NBG_T_INT) { emit_const(VK_INT, NBG_T_INT, 0); break; }
-        const GbOp op = rq->yield_funs[y] == NBG_AGG_BIT_AND ? GB_AND : rq->yield_funs[y] == NBG_AGG_BIT_OR ? GB_OR : GB_XOR;
-        o = GbOut{GE_SLOT, -1, (uint8_t)slot(op, v, 0), 0};
-      }
-    }
-    res->kinds[0][y] = okind;
-    res->col_types[y] = otype;
-  }
-  // ---- the passes
-  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
-  auto* m = const_cast<nbg_rows*>(in);
-  m->build_segs();
-  std::vector<std::pair<uint64_t, uint64_t>> segs;
-  for (auto& sg : m->segs) segs.emplace_back(sg.begin, sg.end - sg.begin);
-  Workspace* inw = in->owned_ws ? in->owned_ws : in->ws;
-  if (!inw) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: the rows have no device workspace");
-  Workspace* ow = nullptr;
-  uint64_t G = 0;
-  std::string err;
-  if (int32_t rc = ws_group_by(inw, E.stream, segs, plan, &ow, &G, &err)) return E.fail(rc, err);
-  res->ws = res->owned_ws = ow;
-  res->count = G;
-  res->derived = in->derived;
-  nbg_rows::TypeBlocks tb;
-  tb.region = 0;
-  tb.blk_cap = G;
-  tb.counts.assign(1, (uint32_t)G);
-  res->blocks.push_back(std::move(tb));
-  for (int c = 0; c < ny; ++c) res->dcols.push_back(ws_row_col(ow, c));
-  *out = res.release();
-  return NBG_OK;
-}
-
-// ============================================================================= ORDER BY / LIMIT
-// OrderByExecutor (src/graph/OrderByExecutor.cpp:94-155) and LimitExecutor
-// (src/graph/LimitExecutor.cpp:18-66) over a device-resident result; the kernels are in orderby.hip.
-// (under the engine lock; nbg_set_op's pass-through shortcuts are this with no factors and no LIMIT)
-static int32_t order_by_locked(Engine& E, const nbg_rows* in, const nbg_order_request* rq, nbg_rows** out) {
-  // LimitExecutor::prepare (:18-28): before anything is executed, whatever the input holds
-  if (rq->has_limit && rq->offset < 0)
-    return E.fail(NBG_E_SYNTAX_ERROR, "skip `" + std::to_string(rq->offset) + "' is illegal");
-  if (rq->has_limit && rq->count < 0)
-    return E.fail(NBG_E_SYNTAX_ERROR, "count `" + std::to_string(rq->count) + "' is illegal");
-  if (in->eng != &E) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: the rows belong to another engine");
-  if (!in->on_device) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: the rows are host-only (not a device result)");
-  if (E.partitioned())
-    return E.fail(NBG_E_UNSUPPORTED, "ORDER BY on a partitioned engine (its rows live on several ranks)");
-  const int nf = rq->num_factors, nc = in->ncols;
-  if (nf < 0) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: negative factor count");
-  // the result carries the input's columns: one kind and one spelling of constants per column
-  std::unique_ptr<nbg_rows> res(gb_new_rows(E, nc));
-  res->derived = in->derived;
-  bool mixed = false, respelt = false;
-  for (int c = 0; c < nc; ++c) {
-    const int k = in->col_kind(c);
-    mixed = mixed || k < 0;
-    res->kinds[0][c] = k < 0 ? VK_INT : (VKind)k;
-    res->col_types[c] = c < (int)in->col_types.size() && in->col_types[c] ? in->col_types[c] : gb_natural_type(res->kinds[0][c]);
-    bool have = false;
-    for (auto& cs : in->const_str) {
-      if ((int)cs.size() <= c) continue;
-      respelt = respelt || (have && res->const_str[0][c] != cs[c]);
-      res->const_str[0][c] = cs[c];
-      have = true;
-    }
-  }
-  if (!in->count) {   // OrderByExecutor::beforeExecute (:137-139) and LimitExecutor: no rows, no check
-    *out = res.release();
-    return NBG_OK;
-  }
-  if (!rq->input_names || (nf > 0 && (!rq->factor_names || !rq->factor_desc)))
-    return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: null argument");
-  if (nf > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: more than NBG_MAX_YIELDS factors");
-  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: the rows have no columns");
-  std::vector<std::string> names;
-  for (int c = 0; c < nc; ++c) {
-    if (!rq->input_names[c]) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: null input column name");
-    names.emplace_back(rq->input_names[c]);
-  }
-  ObPlan plan;
-  plan.nf = nf;
-  plan.ncols = nc;
-  for (int f = 0; f < nf; ++f) {   // getFieldIndex: the first column of that name (:140-152)
-    if (!rq->factor_names[f]) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: null factor name");
-    auto it = std::find(names.begin(), names.end(), std::string(rq->factor_names[f]));
-    if (it == names.end())
-      return E.fail(NBG_E_EXECUTION_ERROR, std::string("Field (") + rq->factor_names[f] + ") not exist in input schema.");
-    plan.col[f] = (int8_t)(it - names.begin());
-    plan.desc[f] = rq->factor_desc[f] != 0;
-  }
-  // ---- device scope
-  if (in->misaligned || in->float_col)
-    return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: the input's row schema re-reads its columns (misaligned or FLOAT)");
-  if (mixed) return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: a column mixes value kinds between OVER types");
-  if (respelt) return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: a string column spells different constants per OVER type");
-  for (int f = 0; f < nf; ++f) {
-    const int c = plan.col[f];
-    plan.dbl[f] = res->kinds[0][c] == VK_DOUBLE;
-    // dictionary codes order as their strings do (loader.cpp: the dictionary is sorted by
-    // std::string::operator<); a derived code or an out-of-dictionary constant does not
-    if (res->kinds[0][c] == VK_STRING && (!in->derived.empty() || !res->const_str[0][c].empty()))
-      return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: factor `" + names[c] + "' can hold strings outside the dictionary");
-  }
-  // ---- the window (LimitExecutor.cpp:30-66)
-  const uint64_t total = in->count;
-  plan.has_limit = rq->has_limit != 0;
-  plan.lo = 0;
-  plan.hi = total;
-  if (plan.has_limit) {
-    const uint64_t off = (uint64_t)rq->offset, cnt = (uint64_t)rq->count;
-    if (cnt == 0 || total <= off) {
-      *out = res.release();
-      return NBG_OK;
-    }
-    plan.lo = off;
-    plan.hi = cnt > total - off ? total : off + cnt;   // (off + cnt saturates)
-  }
-  if (plan.hi - plan.lo > 0xFFFFFFFFull)   // (a result segment's row count is 32 bits)
-    return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: a result of 2^32 rows or more");
-  // ---- the passes
-  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
-  auto* m = const_cast<nbg_rows*>(in);
-  m->build_segs();
-  std::vector<std::pair<uint64_t, uint64_t>> segs;
-  for (auto& sg : m->segs)
-    if (sg.end > sg.begin) segs.emplace_back(sg.begin, sg.end - sg.begin);
-  Workspace* inw = in->owned_ws ? in->owned_ws : in->ws;
-  if (!inw) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: the rows have no device workspace");
-  Workspace* ow = nullptr;
-  std::string err;
-  if (int32_t rc = ws_order_by(inw, E.stream, segs, plan, &ow, &E.ob_prof, &err)) return E.fail(rc, err);
-  const uint64_t n = plan.hi - plan.lo;
-  res->ws = res->owned_ws = ow;
-  res->count = n;
-  nbg_rows::TypeBlocks tb;
-  tb.region = 0;
-  tb.blk_cap = n;
-  tb.counts.assign(1, (uint32_t)n);
-  res->blocks.push_back(std::move(tb));
-  for (int c = 0; c < nc; ++c) res->dcols.push_back(ws_row_col(ow, c));
-  *out = res.release();
-  return NBG_OK;
-}
-
-int32_t nbg_order_by(nbg_engine* h, const nbg_rows* in, const nbg_order_request* rq, nbg_rows** out) {
-  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
-  *out = nullptr;
-  Engine& E = h->e;
-  std::lock_guard<std::mutex> lg(E.mu);
-  return order_by_locked(E, in, rq, out);
-}
-
-// ============================================================================= UNION / INTERSECT / MINUS
-// SetExecutor (src/graph/SetExecutor.cpp:98-383) over two device-resident results; the kernels
-// are in setops.hip.
-int32_t nbg_set_op(nbg_engine* h, const nbg_rows* left, const nbg_rows* right, const nbg_set_request* rq,
-                   nbg_rows** out) {
-  if (!h || !left || !right || !rq || !out) return NBG_E_INVALID_ARGUMENT;
-  *out = nullptr;
-  Engine& E = h->e;
-  std::lock_guard<std::mutex> lg(E.mu);
-  if (rq->op < NBG_SET_UNION || rq->op > NBG_SET_MINUS) return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: unknown operator");
-  if (left->eng != &E || right->eng != &E)
-    return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: the rows belong to another engine");
-  if (!left->on_device || !right->on_device)
-    return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: the rows are host-only (not a device result)");
-  if (E.partitioned())
-    return E.fail(NBG_E_UNSUPPORTED, "set operation on a partitioned engine (its rows live on several ranks)");
-  const int nc = left->ncols;
-  if (nc != right->ncols) return E.fail(NBG_E_EXECUTION_ERROR, "Field count not match.");
-  // ---- the empty-input shortcuts (SetExecutor.cpp:137-141, :163-174, :273-277, :327-337): before
-  // any schema check; a side passed on is what ORDER BY without factors and LIMIT makes of it
-  const bool uni = rq->op == NBG_SET_UNION;
-  auto as_it_is = [&](const nbg_rows* side) {
-    std::vector<const char*> names((size_t)std::max(side->ncols, 1), "");
-    nbg_order_request pass{};
-    pass.input_names = names.data();
-    return order_by_locked(E, side, &pass, out);
-  };
-  if (!left->count || !right->count) {
-    if (uni && right->count) return as_it_is(right);
-    if ((uni || rq->op == NBG_SET_MINUS) && left->count) return as_it_is(left);
-    *out = gb_new_rows(E, nc);   // (both empty, INTERSECT with an empty side, MINUS from nothing)
-    return NBG_OK;
-  }
-  // ---- device scope, and the casts (checkSchema / doCasting, :219-262)
-  if (left->misaligned || left->float_col || right->misaligned || right->float_col)
-    return E.fail(NBG_E_UNSUPPORTED, "set operation: an input's row schema re-reads its columns (misaligned or FLOAT)");
-  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: the rows have no columns");
-  std::unique_ptr<nbg_rows> res(gb_new_rows(E, nc));
-  SoPlan plan;
-  plan.op = rq->op;
-  plan.distinct = uni && rq->distinct;
-  plan.ncols = nc;
-  auto type_of = [](const nbg_rows* r, int c, VKind k) {
-    return c < (int)r->col_types.size() && r->col_types[c] ? r->col_types[c] : gb_natural_type(k);
-  };
-  auto int_like = [](int32_t t) { return t == NBG_T_INT || t == NBG_T_VID || t == NBG_T_TIMESTAMP; };
-  for (int c = 0; c < nc; ++c) {
-    const int lk = left->col_kind(c), rk = right->col_kind(c);
-    if (lk < 0 || rk < 0) return E.fail(NBG_E_UNSUPPORTED, "set operation: a column mixes value kinds between OVER types");
-    const int32_t lt = type_of(left, c, (VKind)lk), rt = type_of(right, c, (VKind)rk);
-    if ((lt == NBG_T_STRING) != (rt == NBG_T_STRING))
-      return E.fail(NBG_E_UNSUPPORTED, "set operation: column " + std::to_string(c) + " casts to or from STRING");
-    if (lt == NBG_T_STRING) {
-      // a constant outside the dictionary has a code private to its result: nothing to compare it by
-      for (const nbg_rows* r : {left, right})
-        for (auto& cs : r->const_str)
-          if ((int)cs.size() > c && !cs[c].empty())
-            return E.fail(NBG_E_UNSUPPORTED, "set operation: string column " + std::to_string(c) +
-                                                 " carries a constant outside the dictionary");
-    }
-    res->kinds[0][c] = (VKind)lk;
-    res->col_types[c] = lt;
-    plan.dbl[c] = lt == NBG_T_DOUBLE;
-    uint8_t cast = SO_KEEP;
-    if (lt != rt) {
-      if (int_like(lt)) cast = rt == NBG_T_DOUBLE ? SO_D2I : rt == NBG_T_BOOL ? SO_B2I : SO_KEEP;
-      else if (lt == NBG_T_DOUBLE) cast = rt == NBG_T_BOOL ? SO_B2D : SO_I2D;
-      else if (lt == NBG_T_BOOL) cast = rt == NBG_T_DOUBLE ? SO_D2B : SO_I2B;
-    }
-    plan.cast[c] = cast;
-  }
-  // the derived strings of both inputs (their codes are content hashes, the same in every result)
-  res->derived = left->derived;
-  for (auto& kv : right->derived) {
-    auto ins = res->derived.emplace(kv.first, kv.second);
-    if (!ins.second && ins.first->second != kv.second) return E.fail(NBG_E_EXECUTION_ERROR, "derived-string hash collision");
-  }
-  // ---- the passes
-  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
-  std::vector<std::pair<uint64_t, uint64_t>> segs[2];
-  Workspace* inw[2] = {nullptr, nullptr};
-  const nbg_rows* sides[2] = {left, right};
-  for (int s = 0; s < 2; ++s) {
-    auto* m = const_cast<nbg_rows*>(sides[s]);
-    m->build_segs();
-    for (auto& sg : m->segs)
-      if (sg.end > sg.begin) segs[s].emplace_back(sg.begin, sg.end - sg.begin);
-    inw[s] = m->owned_ws ? m->owned_ws : m->ws;
-    if (!inw[s]) return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: the rows have no device workspace");
-  }
-  Workspace* ow = nullptr;
-  uint64_t n = 0;
-  std::string err;
-  if (int32_t rc = ws_set_op(inw[0], inw[1], E.stream, segs[0], segs[1], plan, &ow, &n, &E.so_prof, &err))
-    return E.fail(rc, err);
-  if (ow) {
-    res->ws = res->owned_ws = ow;
-    res->count = n;
-    nbg_rows::TypeBlocks tb;
-    tb.region = 0;
-    tb.blk_cap = n;
-    tb.counts.assign(1, (uint32_t)n);
-    res->blocks.push_back(std::move(tb));
-    for (int c = 0; c < nc; ++c) res->dcols.push_back(ws_row_col(ow, c));
-  }
-  *out = res.release();
-  return NBG_OK;
-}
-
-// ============================================================================= YIELD ... WHERE
-// YieldExecutor::executeInputs (src/graph/YieldExecutor.cpp:178-282) over a device-resident result;
-// the kernels are in yieldrows.hip and, beside the interpreter, kernels.hip.
-namespace {
-
-// what a WHERE / YIELD tree references (ExpressionContext's has*Prop and variables())
-struct YrRefs {
-  bool graph = false;                    // $^, $$ or an edge property
-  bool input = false;
-  std::set<std::string> vars;
-  std::vector<std::string> props;        // $- / $var column names, in evaluation order
-};
-void yr_refs(const Node& n, YrRefs* r) {
-  switch (n.kind) {
-    case EK_SRCPROP: case EK_DSTPROP: case EK_ALIAS: case EK_RANK: case EK_DST: case EK_SRCID: case EK_TYPE:
-      r->graph = true;
-      break;
-    case EK_INPUT:
-      r->input = true;
-      r->props.push_back(n.prop);
-      break;
-    case EK_VAR:
-      r->vars.insert(n.alias);
-      r->props.push_back(n.prop);
-      break;
-    default: break;
-  }
-  for (auto& k : n.kids)
-    if (k) yr_refs(*k, r);
-}
-
-}  // namespace
-
-int32_t nbg_yield(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq, nbg_rows** out) {
-  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
-  *out = nullptr;
-  Engine& E = h->e;
-  std::lock_guard<std::mutex> lg(E.mu);
-  // ---- 1. arguments
-  if (rq->num_yields < 1) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: no YIELD column");
-  if (!rq->input_names || !rq->yield_exprs || !rq->yield_lens) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: null argument");
-  if (in->eng != &E) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: the rows belong to another engine");
-  if (!in->on_device) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: the rows are host-only (not a device result)");
-  const int nc = in->ncols;
-  std::vector<std::string> names;
-  for (int c = 0; c < nc; ++c) {
-    if (!rq->input_names[c]) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: null input column name");
-    names.emplace_back(rq->input_names[c]);
-  }
-  std::string err;
-  std::unique_ptr<Node> where;
-  if (rq->where && rq->where_len) {
-    where = decode_expr(rq->where, rq->where_len, &err);
-    if (!where) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: WHERE: " + err);
-  }
-  std::vector<std::unique_ptr<Node>> given;
-  for (int y = 0; y < rq->num_yields; ++y) {
-    if (!rq->yield_exprs[y] || !rq->yield_lens[y]) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: an empty expression");
-    given.push_back(decode_expr(rq->yield_exprs[y], rq->yield_lens[y], &err));
-    if (!given.back()) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: " + err);
-    if (rq->yield_funs && (rq->yield_funs[y] < NBG_AGG_NONE || rq->yield_funs[y] > NBG_AGG_BIT_XOR))
-      return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: unknown function");
-  }
-  // ---- 2.
-  if (E.partitioned()) return E.fail(NBG_E_UNSUPPORTED, "YIELD on a partitioned engine (its rows live on several ranks)");
-  // ---- `$-.*' / `$var.*' (YieldClauseWrapper::prepare): every input column, in order
-  std::vector<std::unique_ptr<Node>> yields;
-  std::vector<int32_t> funs;
-  YrRefs refs;
-  if (where) yr_refs(*where, &refs);
-  for (int y = 0; y < rq->num_yields; ++y) {
-    Node& n = *given[y];
-    const int32_t f = rq->yield_funs ? rq->yield_funs[y] : NBG_AGG_NONE;
-    if ((n.kind == EK_INPUT || n.kind == EK_VAR) && n.prop == "*") {
-      if (n.kind == EK_INPUT) refs.input = true;
-      else refs.vars.insert(n.alias);
-      for (int c = 0; c < nc; ++c) {
-        auto col = std::make_unique<Node>();
-        col->kind = n.kind;
-        col->alias = n.alias;
-        col->prop = names[c];
-        yields.push_back(std::move(col));
-        funs.push_back(f);
-      }
-      continue;
-    }
-    yr_refs(n, &refs);
-    yields.push_back(std::move(given[y]));
-    funs.push_back(f);
-  }
-  const int ny = (int)yields.size();
-  // ---- 3. checkAggFun (:33-58), syntaxCheck (:116-122)
-  bool agg = false;
-  for (int32_t f : funs) agg = agg || f != NBG_AGG_NONE;
-  if (agg)
-    for (int y = 0; y < ny; ++y)
-      if ((yields[y]->kind == EK_INPUT || yields[y]->kind == EK_VAR) && funs[y] == NBG_AGG_NONE)
-        return E.fail(NBG_E_SYNTAX_ERROR,
-                      "Input columns without aggregation are not supported in YIELD statement without GROUP BY, near `" +
-                          yields[y]->prop + "'");
-  if (refs.graph) return E.fail(NBG_E_SYNTAX_ERROR, "Only support input and variable in yield sentence.");
-  // ---- 4. (:124-135)
-  if (refs.input && !refs.vars.empty()) return E.fail(NBG_E_EXECUTION_ERROR, "Not support both input and variable.");
-  if (refs.vars.size() > 1) return E.fail(NBG_E_EXECUTION_ERROR, "Only one variable allowed to use.");
-  // ---- 5. no rows: one column per YIELD
-  if (!in->count) {
-    *out = gb_new_rows(E, std::min(ny, (int)MAX_YIELDS));
-    return NBG_OK;
-  }
-  // ---- 6. getOutputSchema (:298-316): getFieldIndex, the first column of that name
-  auto find_col = [&](const std::string& n) {
-    auto it = std::find(names.begin(), names.end(), n);
-    return it == names.end() ? -1 : (int)(it - names.begin());
-  };
-  for (const std::string& p : refs.props)
-    if (find_col(p) < 0)
-      return E.fail(NBG_E_EXECUTION_ERROR,
-                    "column `" + p + "' not exist in " + (refs.vars.empty() ? "input." : "variable."));
-  // ---- 7. device scope
-  if (agg) return E.fail(NBG_E_UNSUPPORTED, "YIELD: aggregate functions without GROUP BY");
-  if (in->misaligned || in->float_col)
-    return E.fail(NBG_E_UNSUPPORTED, "YIELD: the input's row schema re-reads its columns (misaligned or FLOAT)");
-  if (ny > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "YIELD: more than NBG_MAX_YIELDS columns");
-  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: the rows have no columns");
-  if (in->count > 0xFFFFFFFFull) return E.fail(NBG_E_UNSUPPORTED, "YIELD: an input of 2^32 rows or more");
-  std::vector<VKind> kinds(nc, VK_INT);
-  std::vector<uint8_t> outside(nc, 0), respelt(nc, 0);   // string columns: beyond the dictionary; spelt per OVER type
-  std::vector<std::string> spell(nc);
-  for (int c = 0; c < nc; ++c) {
-    const int k = in->col_kind(c);
-    kinds[c] = k < 0 ? VK_INT : (VKind)k;
-    bool have = false;
-    for (auto& cs : in->const_str) {
-      if ((int)cs.size() <= c) continue;
-      respelt[c] = respelt[c] || (have && spell[c] != cs[c]);
-      spell[c] = cs[c];
-      have = true;
-      outside[c] = outside[c] || !cs[c].empty();
-    }
-    outside[c] = outside[c] || !in->derived.empty();
-  }
-  // a use: `bare' is a YIELD column that is exactly the input column
-  auto check_use = [&](int c, bool bare) -> int32_t {
-    if (in->col_kind(c) < 0) return E.fail(NBG_E_UNSUPPORTED, "YIELD: column `" + names[c] + "' mixes value kinds");
-    if (kinds[c] != VK_STRING) return NBG_OK;
-    if (!bare && outside[c])
-      return E.fail(NBG_E_UNSUPPORTED, "YIELD: column `" + names[c] + "' can hold strings outside the dictionary");
-    if (bare && respelt[c])
-      return E.fail(NBG_E_UNSUPPORTED, "YIELD: column `" + names[c] + "' spells different constants per OVER type");
-    return NBG_OK;
-  };
-  {
-    YrRefs wr;
-    if (where) yr_refs(*where, &wr);
-    for (const std::string& p : wr.props)
-      if (int32_t rc = check_use(find_col(p), false)) return rc;
-    for (int y = 0; y < ny; ++y) {
-      const bool bare = yields[y]->kind == EK_INPUT || yields[y]->kind == EK_VAR;
-      YrRefs yr;
-      yr_refs(*yields[y], &yr);
-      for (const std::string& p : yr.props)
-        if (int32_t rc = check_use(find_col(p), bare)) return rc;
-    }
-  }
-  // ---- compile: WHERE first, then the YIELDs, one program for every row
-  static const std::vector<int32_t> no_over;
-  if (E.max_dict_len_of != E.snap.strings.size()) {
-    E.max_dict_len = 0;
-    for (const std::string& x : E.snap.strings) E.max_dict_len = std::max<uint64_t>(E.max_dict_len, x.size());
-    E.max_dict_len_of = E.snap.strings.size();
-  }
-  CompileEnv cenv{};
-  cenv.etype = 0;
-  cenv.over = &no_over;
-  cenv.edges = &E.edges;
-  cenv.strings = &E.snap.strings;
-  cenv.tags = &E.tags;
-  cenv.input_names = &names;
-  cenv.input_kinds = &kinds;
-  cenv.max_dict_len = E.max_dict_len;
-  cenv.rows = true;
-  ProgramBuilder pb;
-  YrPlan plan;
-  plan.ncols = ny;
-  bool where_false = false;
-  auto scope = [&](int32_t rc) { return E.fail(rc, "YIELD: " + err); };
-  if (where) {
-    Compiled c;
-    if (int32_t rc = compile_expr(*where, cenv, pb, &c, &err)) return scope(rc);
-    if (c.is_const) {
-      bool tv;
-      switch (c.kind) {   // Expression::asBool
-        case VK_STRING: tv = c.const_str.empty(); break;
-        case VK_DOUBLE: { double d; memcpy(&d, &c.const_bits, 8); tv = d != 0.0; break; }
-        default: tv = c.const_bits != 0;
-      }
-      where_false = !tv;
-      pb.code.clear();
-    } else {
-      const int r = c.reg;
-      if (c.kind == VK_INT) pb.code.push_back(Ins{OP_TRUTHY_I, (uint8_t)r, (uint8_t)r, 0, 0, 0});
-      else if (c.kind == VK_DOUBLE) pb.code.push_back(Ins{OP_TRUTHY_F, (uint8_t)r, (uint8_t)r, 0, 0, 0});
-      else if (c.kind == VK_STRING)
-        pb.code.push_back(Ins{OP_TRUTHY_S, (uint8_t)r, (uint8_t)r, 0, 0, string_code(E.snap.strings, "")});
-      plan.where_len = (int)pb.code.size();
-      plan.where_reg = r;
-    }
-    pb.next_reg = 0;   // WHERE registers are dead once its value is read
-  }
-  std::unique_ptr<nbg_rows> res(gb_new_rows(E, ny));
-  res->derived = in->derived;
-  ColTypeEnv tenv;
-  tenv.input_names = &names;
-  tenv.input_kinds = &kinds;
-  std::set<int32_t> direct;   // input columns passed through without the interpreter
-  for (int y = 0; y < ny; ++y) {
-    if (yields[y]->kind == EK_INPUT || yields[y]->kind == EK_VAR) {   // a bare column: copied as it is
-      const int col = find_col(yields[y]->prop);
-      plan.yield_reg[y] = -2 - col;
-      direct.insert(col);
-      res->kinds[0][y] = kinds[col];
-      res->col_types[y] = gb_natural_type(kinds[col]);
-      if (kinds[col] == VK_STRING) res->const_str[0][y] = spell[col];
-      continue;
-    }
-    Compiled c;
-    if (int32_t rc = compile_expr(*yields[y], cenv, pb, &c, &err, true)) return scope(rc);
-    plan.yield_reg[y] = c.is_const ? -1 : c.reg;
-    plan.yield_const[y] = c.is_const ? c.const_bits : 0;
-    res->kinds[0][y] = c.kind;
-    // Collector::getSchema: the value's own type, or a root cast's (yield_column_type's cast rule)
-    res->col_types[y] = yields[y]->kind == EK_CAST ? yield_column_type(*yields[y], tenv) : gb_natural_type(c.kind);
-    if (c.is_const && c.kind == VK_STRING && (c.const_bits & 1)) res->const_str[0][y] = c.const_str;
-  }
-  plan.code = pb.code;
-  plan.data = pb.data;
-  plan.nregs = std::max(1, pb.max_reg);
-  for (const Ins& i : plan.code)
-    if (i.op == OP_SOUT || i.op == OP_SMAT) return E.fail(NBG_E_UNSUPPORTED, "YIELD: an expression that builds a string");
-  if ((int)(plan.code.size() + plan.data.size()) > MAX_PROGRAM) return E.fail(NBG_E_UNSUPPORTED, "YIELD: program too long");
-  if (plan.nregs > interp_max_regs())
-    return E.fail(NBG_E_UNSUPPORTED, "YIELD: expression too deep for the device register file (" + std::to_string(plan.nregs) +
-                                         " registers, " + std::to_string(interp_max_regs()) + " fit the LDS)");
-  if (where_false) {   // a constant-false WHERE: no row, no launch
-    *out = res.release();
-    return NBG_OK;
-  }
-  {
-    std::set<int32_t> wc, yc = direct;
-    for (int pc = 0; pc < (int)plan.code.size(); ++pc)
-      if (plan.code[pc].op == OP_COL) (pc < plan.where_len ? wc : yc).insert(plan.code[pc].aux);
-    plan.where_cols = (int)wc.size();
-    plan.yield_cols = (int)yc.size();
-  }
-  // ---- 8. the passes
-  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
-  plan.str = E.dev_strings();
-  plan.now_sec = (int64_t)time(nullptr);
-  plan.rand_seed = query_rand_seed();
-  auto* m = const_cast<nbg_rows*>(in);
-  m->build_segs();
-  std::vector<std::pair<uint64_t, uint64_t>> segs;
-  for (auto& sg : m->segs)
-    if (sg.end > sg.begin) segs.emplace_back(sg.begin, sg.end - sg.begin);
-  Workspace* inw = in->owned_ws ? in->owned_ws : in->ws;
-  if (!inw) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: the rows have no device workspace");
-  Workspace* ow = nullptr;
-  uint64_t n = 0;
-  if (int32_t rc = ws_yield_rows(inw, E.stream, segs, plan, &ow, &n, &E.yr_prof, &err)) return E.fail(rc, err);
-  if (ow) {
-    res->ws = res->owned_ws = ow;
-    res->count = n;
-    nbg_rows::TypeBlocks tb;
-    tb.region = 0;
-    tb.blk_cap = n;
-    tb.counts.assign(1, (uint32_t)n);
-    res->blocks.push_back(std::move(tb));
-    for (int c = 0; c < ny; ++c) res->dcols.push_back(ws_row_col(ow, c));
-  }
-  *out = res.release();
-  return NBG_OK;
-}
-
-// ============================================================================= FETCH PROP ON <tag>
-// FetchVerticesExecutor / FetchExecutor (src/graph/FetchVerticesExecutor.cpp:19-311,
-// src/graph/FetchExecutor.cpp:14-131) over a device-resident result; the kernels are in
-// fetchrows.hip and, beside the interpreter, kernels.hip.
-namespace {
-
-// what a YIELD tree of a FETCH references (ExpressionContext's has*Prop and aliasProps())
-struct FvRefs {
-  bool graph = false;   // $^ / $$
-  bool input = false;   // $- / $var
-  std::vector<std::pair<std::string, std::string>> alias;   // (alias, prop), in evaluation order
-};
-void fv_refs(const Node& n, FvRefs* r) {
-  switch (n.kind) {
-    case EK_SRCPROP: case EK_DSTPROP: r->graph = true; break;
-    case EK_INPUT: case EK_VAR: r->input = true; break;
-    case EK_ALIAS: case EK_RANK: case EK_DST: case EK_SRCID: case EK_TYPE: r->alias.emplace_back(n.alias, n.prop); break;
-    default: break;
-  }
-  for (auto& k : n.kids)
-    if (k) fv_refs(*k, r);
-}
-
-// a one-segment device result holding `n` rows in `w` (the stages' result form)
-void fv_adopt(nbg_rows* r, Workspace* w, uint64_t n, int ncols) {
-  r->ws = r->owned_ws = w;
-  r->count = n;
-  nbg_rows::TypeBlocks tb;
-  tb.region = 0;
-  tb.blk_cap = n;
-  tb.counts.assign(1, (uint32_t)n);
-  r->blocks.push_back(std::move(tb));
-  for (int c = 0; c < ncols; ++c) r->dcols.push_back(ws_row_col(w, c));
-}
-
-}  // namespace
-
-int32_t nbg_fetch_vertices(nbg_engine* h, const nbg_rows* in, const nbg_fetch_request* rq, nbg_rows** out) {
-  if (!h || !rq || !out) return NBG_E_INVALID_ARGUMENT;
-  *out = nullptr;
-  Engine& E = h->e;
-  std::lock_guard<std::mutex> lg(E.mu);
-  // ---- 1. arguments
-  if (rq->num_yields < 0 || (rq->num_yields > 0 && (!rq->yield_exprs || !rq->yield_lens)))
-    return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null argument");
-  if (in) {
-    if (!rq->input_names || !rq->vid_col) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null argument");
-    if (in->eng != &E) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: the rows belong to another engine");
-    if (!in->on_device) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: the rows are host-only (not a device result)");
-  } else if (!rq->vids && rq->num_vids) {
-    return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null vid list");
-  }
-  if (!E.finalized) return E.fail(NBG_E_STATE, "engine not finalized");
-  const int nc = in ? in->ncols : 1;
-  std::vector<std::string> names;
-  if (in) {
-    for (int c = 0; c < nc; ++c) {
-      if (!rq->input_names[c]) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null input column name");
-      names.emplace_back(rq->input_names[c]);
-    }
-  } else {
-    names.emplace_back("id");
-  }
-  const std::string vid_col = in ? rq->vid_col : "id";
-  std::string err;
-  std::vector<std::unique_ptr<Node>> yields;
-  for (int y = 0; y < rq->num_yields; ++y) {
-    if (!rq->yield_exprs[y] || !rq->yield_lens[y]) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: an empty expression");
-    yields.push_back(decode_expr(rq->yield_exprs[y], rq->yield_lens[y], &err));
-    if (!yields.back()) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: " + err);
-  }
-  // ---- 2.
-  if (E.partitioned()) return E.fail(NBG_E_UNSUPPORTED, "FETCH on a partitioned engine (its rows live on several ranks)");
-  // ---- 3. prepareClauses (:39-50), prepareVids (:79-81)
-  auto tit = E.tags.find(rq->tag_id);
-  const Schema* tsc = tit == E.tags.end() ? nullptr : tit->second.latest();
-  if (!tsc) return E.fail(NBG_E_EXECUTION_ERROR, "tag " + std::to_string(rq->tag_id) + " schema not exist.");
-  const std::string& tag_name = tit->second.name;
-  if (in && vid_col == "*") return E.fail(NBG_E_EXECUTION_ERROR, "Cant not use `*' to reference a vertex id column.");
-  // ---- no YIELD clause: every column of the latest schema, in order (FetchExecutor::setupColumns, :73-90)
-  if (!rq->num_yields)
-    for (const Column& col : tsc->cols) {
-      auto n = std::make_unique<Node>();
-      n->kind = EK_ALIAS;
-      n->alias = tag_name;
-      n->prop = col.name;
-      yields.push_back(std::move(n));
-    }
-  const int ny = (int)yields.size();
-  // ---- 4. prepareYield (FetchExecutor.cpp:50-68), before setupVids: diagnosed for an empty input too
-  FvRefs refs;
-  for (auto& y : yields) fv_refs(*y, &refs);
-  if (refs.graph) return E.fail(NBG_E_SYNTAX_ERROR, "tag.prop and edgetype.prop are supported in fetch sentence.");
-  if (refs.input) return E.fail(NBG_E_SYNTAX_ERROR, "`$-' and `$variable' not supported in fetch yet.");
-  for (auto& ap : refs.alias)
-    if (ap.first != tag_name)
-      return E.fail(NBG_E_SYNTAX_ERROR,
-                    "Near [" + ap.first + "." + ap.second + "], tag or edge should be declared in statement first.");
-  // ---- 5. no rows (onEmptyInputs, FetchExecutor.cpp:99-107): one column per YIELD
-  const uint64_t nin = in ? in->count : rq->num_vids;
-  if (!nin) {
-    *out = gb_new_rows(E, std::min(ny, (int)MAX_YIELDS));
-    return NBG_OK;
-  }
-  // ---- 6. getVIDs -> RowReader::getVid (InterimResult.cpp:29-72, RowReader.cpp:569-576): INT and VID
-  // columns only; getPropNames (:142-153, :110-115); the storage request names a prop the schema lacks
-  int vcol = 0;
-  if (in) {
-    auto it = std::find(names.begin(), names.end(), vid_col);
-    vcol = it == names.end() ? -1 : (int)(it - names.begin());
-    bool ok = vcol >= 0;
-    if (ok) {
-      const int k = in->col_kind(vcol);
-      const int32_t t = vcol < (int)in->col_types.size() && in->col_types[vcol] ? in->col_types[vcol]
-                                                                                : gb_natural_type(k < 0 ? VK_INT : (VKind)k);
-      ok = (k < 0 || k == VK_INT) && (t == NBG_T_INT || t == NBG_T_VID);
-    }
-    if (!ok) return E.fail(NBG_E_EXECUTION_ERROR, "Column `" + vid_col + "' not found");
-  }
-  if (refs.alias.empty()) return E.fail(NBG_E_EXECUTION_ERROR, "No props declared.");
-  for (auto& ap : refs.alias)
-    if (tsc->find(ap.second) < 0) return E.fail(NBG_E_EXECUTION_ERROR, "Get props failed");
-  // ---- 7. device scope
-  if (in && (in->misaligned || in->float_col))
-    return E.fail(NBG_E_UNSUPPORTED, "FETCH: the input's row schema re-reads its columns (misaligned or FLOAT)");
-  if (in && in->col_kind(vcol) < 0) return E.fail(NBG_E_UNSUPPORTED, "FETCH: column `" + vid_col + "' mixes value kinds");
-  if (ny > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "FETCH: more than NBG_MAX_YIELDS columns");
-  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: the rows have no columns");
-  if (nin > 0xFFFFFFFFull) return E.fail(NBG_E_UNSUPPORTED, "FETCH: an input of 2^32 rows or more");
-  auto dit = E.snap.tags.find(rq->tag_id);
-  if (dit == E.snap.tags.end() || !dit->second.decoded || !E.snap.d_tcols || !E.snap.d_tpres || !E.snap.d_vids)
-    return E.fail(NBG_E_UNSUPPORTED, "FETCH: tag tables missing");
-  const DevTag& dtag = dit->second;
-  // ---- compile: the YIELDs, one program for every found row
-  static const std::vector<int32_t> no_over;
-  if (E.max_dict_len_of != E.snap.strings.size()) {
-    E.max_dict_len = 0;
-    for (const std::string& x : E.snap.strings) E.max_dict_len = std::max<uint64_t>(E.max_dict_len, x.size());
-    E.max_dict_len_of = E.snap.strings.size();
-  }
-  CompileEnv cenv{};
-  cenv.etype = 0;
-  cenv.over = &no_over;
-  cenv.edges = &E.edges;
-  cenv.strings = &E.snap.strings;
-  cenv.tags = &E.tags;
-  cenv.dtags = &E.snap.tags;
-  cenv.max_dict_len = E.max_dict_len;
-  cenv.rows = true;
-  cenv.fetch_tag = &tag_name;
-  ProgramBuilder pb;
-  FvPlan plan;
-  plan.y.ncols = ny;
-  plan.vid_col = vcol;
-  plan.pres = dtag.decoded;
-  std::unique_ptr<nbg_rows> res(gb_new_rows(E, ny));
-  ColTypeEnv tenv;
-  std::set<int32_t> tcols_read;
-  for (int y = 0; y < ny; ++y) {
-    const Node& n = *yields[y];
-    if (n.kind == EK_ALIAS) {   // a bare `tag.prop': the found vertex's column as it is
-      const int col = tsc->find(n.prop);
-      if (col >= (int)dtag.kind.size()) return E.fail(NBG_E_UNSUPPORTED, "FETCH: tag tables missing");
-      plan.y.yield_reg[y] = -2 - (dtag.col_base + col);
-      tcols_read.insert(dtag.col_base + col);
-      res->kinds[0][y] = dtag.kind[col];
-      res->col_types[y] = tsc->cols[col].type;   // FetchExecutor::prepareYield, :37-42
-      if (res->col_types[y] == NBG_T_FLOAT) return E.fail(NBG_E_UNSUPPORTED, "FETCH: a bare FLOAT prop (a FLOAT result column)");
-      continue;
-    }
-    Compiled c;
-    if (int32_t rc = compile_expr(n, cenv, pb, &c, &err, true)) return E.fail(rc, "FETCH: " + err);
-    plan.y.yield_reg[y] = c.is_const ? -1 : c.reg;
-    plan.y.yield_const[y] = c.is_const ? c.const_bits : 0;
-    res->kinds[0][y] = c.kind;
-    res->col_types[y] = n.kind == EK_CAST ? yield_column_type(n, tenv) : gb_natural_type(c.kind);   // :43-47
-    if (!res->col_types[y]) res->col_types[y] = gb_natural_type(c.kind);
-    if (c.is_const && c.kind == VK_STRING && (c.const_bits & 1)) res->const_str[0][y] = c.const_str;
-  }
-  plan.y.code = pb.code;
-  plan.y.data = pb.data;
-  plan.y.nregs = std::max(1, pb.max_reg);
-  for (const Ins& i : plan.y.code) {
-    if (i.op == OP_SOUT || i.op == OP_SMAT) return E.fail(NBG_E_UNSUPPORTED, "FETCH: an expression that builds a string");
-    if (i.op == OP_TAGS_E) tcols_read.insert(i.aux & 0xFFFF);
-  }
-  if ((int)(plan.y.code.size() + plan.y.data.size()) > MAX_PROGRAM) return E.fail(NBG_E_UNSUPPORTED, "FETCH: program too long");
-  if (plan.y.nregs > interp_max_regs())
-    return E.fail(NBG_E_UNSUPPORTED, "FETCH: expression too deep for the device register file (" +
-                                         std::to_string(plan.y.nregs) + " registers, " + std::to_string(interp_max_regs()) +
-                                         " fit the LDS)");
-  plan.tag_cols = (int)tcols_read.size();
-  // ---- 8. the passes
-  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
-  plan.y.str = E.dev_strings();
-  plan.y.now_sec = (int64_t)time(nullptr);
-  plan.y.rand_seed = query_rand_seed();
-  plan.vids = E.snap.d_vids;
-  plan.nv = E.snap.nv;
-  plan.visible = E.snap.d_visible;
-  plan.tcols = E.snap.d_tcols;
-  plan.tpres = E.snap.d_tpres;
-  // (a knob of tools/fetch_probe.py alone, like NBG_SP_*: not part of the interface.  Read per call,
-  // so the probe can A/B both searches in one process; a getenv beside milliseconds of kernels)
-  if (const char* s = getenv("NBG_FETCH_SEARCH")) plan.search = !strcmp(s, "two-level") ? 2 : 0;
-  struct WsGuard {
-    Workspace* w = nullptr;
-    ~WsGuard() { if (w) ws_destroy(w); }
-  } first;
-  std::vector<std::pair<uint64_t, uint64_t>> segs;
-  Workspace* inw = nullptr;
-  if (in) {
-    auto* m = const_cast<nbg_rows*>(in);
-    m->build_segs();
-    for (auto& sg : m->segs)
-      if (sg.end > sg.begin) segs.emplace_back(sg.begin, sg.end - sg.begin);
-    inw = in->owned_ws ? in->owned_ws : in->ws;
-    if (!inw) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: the rows have no device workspace");
-  } else {   // the literal vids: ws_fetch_vertices uploads them into a temporary one-column result
-    segs.emplace_back(0, nin);
-  }
-  Workspace* ow = nullptr;
-  uint64_t n = 0;
-  if (int32_t rc = ws_fetch_vertices(inw, in ? nullptr : rq->vids, E.stream, segs, plan, &ow, &n, &E.fv_prof, &err)) return E.fail(rc, err);
-  // ---- YIELD DISTINCT (processResult's uniqResult, :159, :221-228): one row per distinct output
-  // row, through nbg_set_op's row table: the UNION DISTINCT of the result's two halves
-  if (ow && rq->distinct && n > 1) {
-    first.w = ow;
-    SoPlan sp;
-    sp.op = NBG_SET_UNION;
-    sp.distinct = 1;
-    sp.ncols = ny;
-    for (int c = 0; c < ny; ++c) sp.dbl[c] = res->kinds[0][c] == VK_DOUBLE;   // (-0.0 == 0.0, as nbg_set_op)
-    const uint64_t half = n / 2;
-    ow = nullptr;
-    if (int32_t rc = ws_set_op(first.w, first.w, E.stream, {{0, half}}, {{half, n - half}}, sp, &ow, &n, &E.so_prof, &err))
-      return E.fail(rc, err);
-  }
-  if (ow) fv_adopt(res.get(), ow, n, ny);
-  *out = res.release();
-  return NBG_OK;
-}
-
 int32_t nbg_set_path_replica(nbg_engine* h, int32_t mode) {
   if (!h || mode < 0 || mode > 1) return NBG_E_INVALID_ARGUMENT;
   Engine& E = h->e;
@@ -3217,14 +2054,10 @@ int32_t nbg_profile(nbg_engine* h, int32_t enable) {
   if (!E.ws) return E.fail(NBG_E_STATE, "engine not finalized");
   const int mode = enable == 2 ? 2 : (enable != 0 ? 1 : 0);
   ws_profile(E.ws, mode);
-  if (mode) E.ob_prof = ObProf{};   // (enabling resets the counters, as ws_profile does)
-  E.ob_prof.on = mode == 1;
-  if (mode) E.so_prof = SoProf{};
-  E.so_prof.on = mode == 1;
-  if (mode) E.yr_prof = YrProf{};
-  E.yr_prof.on = mode == 1;
-  if (mode) E.fv_prof = FvProf{};
-  E.fv_prof.on = mode == 1;
+  for_stage_profs(E, [&](const char* const*, auto& p) {   // (enabling resets the counters, as ws_profile does)
+    if (mode) p = {};
+    p.on = mode == 1;
+  });
   // the one-pair SHORTEST contexts (device-driven chains): their launches and algorithmic bytes
   for (Engine* P : {&E, E.rep.get()}) {   // (and the FIND PATH replica's)
     if (!P) continue;
@@ -3253,30 +2086,14 @@ int32_t nbg_profile_read(const nbg_engine* h, nbg_kernel_stat* out, int32_t cap)
     out[n].total_ms = ms[k];
     out[n].algo_bytes = bytes[k];
   }
-  for (int k = 0; k < OB_KINDS && n < cap; ++k, ++n) {   // nbg_order_by's kernels (orderby.hip)
-    out[n].name = kObKernelNames[k];
-    out[n].launches = E.ob_prof.launches[k];
-    out[n].total_ms = E.ob_prof.ms[k];
-    out[n].algo_bytes = E.ob_prof.bytes[k];
-  }
-  for (int k = 0; k < SO_KINDS && n < cap; ++k, ++n) {   // nbg_set_op's kernels (setops.hip)
-    out[n].name = kSoKernelNames[k];
-    out[n].launches = E.so_prof.launches[k];
-    out[n].total_ms = E.so_prof.ms[k];
-    out[n].algo_bytes = E.so_prof.bytes[k];
-  }
-  for (int k = 0; k < YR_KINDS && n < cap; ++k, ++n) {   // nbg_yield's kernels (yieldrows.hip)
-    out[n].name = kYrKernelNames[k];
-    out[n].launches = E.yr_prof.launches[k];
-    out[n].total_ms = E.yr_prof.ms[k];
-    out[n].algo_bytes = E.yr_prof.bytes[k];
-  }
-  for (int k = 0; k < FV_KINDS && n < cap; ++k, ++n) {   // nbg_fetch_vertices' kernels (fetchrows.hip)
-    out[n].name = kFvKernelNames[k];
-    out[n].launches = E.fv_prof.launches[k];
-    out[n].total_ms = E.fv_prof.ms[k];
-    out[n].algo_bytes = E.fv_prof.bytes[k];
-  }
+  for_stage_profs(E, [&](const char* const* names, const auto& p) {
+    for (int k = 0; k < (int)std::size(p.ms) && n < cap; ++k, ++n) {
+      out[n].name = names[k];
+      out[n].launches = p.launches[k];
+      out[n].total_ms = p.ms[k];
+      out[n].algo_bytes = p.bytes[k];
+    }
+  });
   return n;
 }
 

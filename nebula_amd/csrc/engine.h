@@ -1,5 +1,6 @@
 // Engine object behind the C ABI.
 #pragma once
+#include <algorithm>
 #include <atomic>
 #include <memory>
 #include <mutex>
@@ -56,13 +57,21 @@ struct Engine {
   hipStream_t batch_stream = nullptr;
   uint64_t max_dict_len = 0;            // the longest dictionary string (derived-string arena bound),
   uint64_t max_dict_len_of = ~0ull;     //   computed for a dictionary of this many strings
+  uint64_t refresh_max_dict_len() {     // (cached: the dictionary is fixed after finalize)
+    if (max_dict_len_of != snap.strings.size()) {
+      max_dict_len = 0;
+      for (const std::string& x : snap.strings) max_dict_len = std::max<uint64_t>(max_dict_len, x.size());
+      max_dict_len_of = snap.strings.size();
+    }
+    return max_dict_len;
+  }
   uint64_t row_reserve = 0;             // result rows of the largest prepared GO statement (new
   int col_reserve = 0;                  // query workspaces are sized for it before their first query)
   int prof_mode = 0;
-  ObProf ob_prof;                       // nbg_order_by's kernels (nbg_profile mode 1)
-  SoProf so_prof;                       // nbg_set_op's kernels
-  YrProf yr_prof;                       // nbg_yield's kernels
-  FvProf fv_prof;                       // nbg_fetch_vertices' kernels
+  StageProf<OB_KINDS> ob_prof;                       // nbg_order_by's kernels (nbg_profile mode 1)
+  StageProf<SO_KINDS> so_prof;                       // nbg_set_op's kernels
+  StageProf<YR_KINDS> yr_prof;                       // nbg_yield's kernels
+  StageProf<FV_KINDS> fv_prof;                       // nbg_fetch_vertices' kernels
   // pinned host blocks of fetched GO rows (nbg_rows_fetch), reused across queries
   std::mutex pinned_mu;
   std::vector<std::pair<size_t, void*>> pinned_free;
@@ -154,6 +163,15 @@ struct Engine {
   int32_t upload_strings();         // the dictionary's device tables (engine_ready)
   DevStrings dev_strings() const;   // ... as the kernels read them (no arena)
 };
+
+// the stages' profile records, in nbg_profile_read's order (after the chain kernels)
+template <class Eng, class F>
+void for_stage_profs(Eng& E, F f) {
+  f(kObKernelNames, E.ob_prof);   // nbg_order_by's kernels (orderby.hip)
+  f(kSoKernelNames, E.so_prof);   // nbg_set_op's (setops.hip)
+  f(kYrKernelNames, E.yr_prof);   // nbg_yield's (yieldrows.hip)
+  f(kFvKernelNames, E.fv_prof);   // nbg_fetch_vertices' (fetchrows.hip)
+}
 
 int32_t engine_ready(Engine& E);   // workspace (+ partition buffers) after finalize / snapshot load
 // replica.hip: the FIND PATH replica of a partitioned engine (collective; no replica when it does

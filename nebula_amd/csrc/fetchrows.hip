@@ -27,20 +27,10 @@ namespace nbg {
 const char* const kFvKernelNames[FV_KINDS] = {"k_fv_resolve", "k_fv_emit"};
 
 int32_t ws_fetch_vertices(Workspace* inw, const int64_t* host_vids, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
-                          const FvPlan& plan, Workspace** outw, uint64_t* rows, FvProf* prof, std::string* err) {
+                          const FvPlan& plan, Workspace** outw, uint64_t* rows, StageProf<FV_KINDS>* prof, std::string* err) {
   *outw = nullptr;
   *rows = 0;
-  hipError_t he = hipSuccess;
-  const char* what = "";
-  auto failed = [&](hipError_t e, const char* w) {
-    he = e;
-    what = w;
-    return e != hipSuccess;
-  };
-  auto code = [&]() -> int32_t {
-    if (err) *err = std::string("FETCH: ") + what + ": " + hipGetErrorString(he);
-    return he == hipErrorOutOfMemory ? NBG_E_OUT_OF_MEMORY : NBG_E_DEVICE;
-  };
+  StageStatus cs("FETCH");
   const YrPlan& yp = plan.y;
   uint64_t n = 0;
   for (auto& sg : segs) n += sg.second;
@@ -51,75 +41,33 @@ int32_t ws_fetch_vertices(Workspace* inw, const int64_t* host_vids, hipStream_t 
     return NBG_E_INVALID_ARGUMENT;
   }
 
-  // the result: a workspace holding nothing but its rows (what the row accessors read)
-  struct WsGuard {
-    Workspace* w = nullptr;
-    ~WsGuard() { if (w) ws_destroy(w); }
-  } res, lit;
-  auto new_rows = [&](WsGuard& g, uint64_t nrows, int ncols) {
-    g.w = new Workspace();
-    g.w->stream = stream;
-    hipError_t e = hipMalloc((void**)&g.w->d_row_cols, MAX_YIELDS * sizeof(int64_t*));
-    if (e == hipSuccess) e = ws_reserve_rows(g.w, nrows, ncols);
-    if (e != hipSuccess) (void)hipGetLastError();
-    return e;
-  };
+  RowsWs res, lit;
   if (!inw) {   // a literal vid list: a temporary one-column result on the same path
     if (!host_vids || segs.size() != 1 || segs[0].first != 0) {
       if (err) *err = "FETCH: no input";
       return NBG_E_INVALID_ARGUMENT;
     }
-    if (failed(new_rows(lit, n, 1), "vid rows") ||
-        failed(hipMemcpyAsync(ws_row_col(lit.w, 0), host_vids, n * 8, hipMemcpyHostToDevice, stream), "vid upload") ||
-        failed(hipStreamSynchronize(stream), "vid upload"))
-      return code();
+    if (cs.failed(lit.reserve(stream, n, 1), "vid rows") ||
+        cs.failed(hipMemcpyAsync(ws_row_col(lit.w, 0), host_vids, n * 8, hipMemcpyHostToDevice, stream), "vid upload") ||
+        cs.failed(hipStreamSynchronize(stream), "vid upload"))
+      return cs.code(err);
     inw = lit.w;
   }
 
   StageScratch sc;   // (declared before the timer: the timer's events are resolved first)
-  StageTimer<FvProf> tm{prof, stream, {}, nullptr};
-  const std::vector<uint64_t> chunks = stage_chunks(segs, 0, n);
-  const uint32_t nchunks = (uint32_t)(chunks.size() / 3);
-  const unsigned grid = std::min<unsigned>(std::max<uint32_t>(nchunks, 1), STAGE_GRID);
-  std::vector<Ins> image(yp.code);
-  image.insert(image.end(), yp.data.begin(), yp.data.end());
-  uint64_t* d_chunks = nullptr;
-  Ins* d_prog = nullptr;
+  StageTimer<FV_KINDS> tm{prof, stream, {}, nullptr};
+  StageChunks ch;
+  FvArgs f{};
+  YrArgs& a = f.y;
   YrState* st = nullptr;
   uint32_t* ccount = nullptr;
   uint32_t* cbase = nullptr;
-  FvArgs f{};
-  // (a pageable source is staged by the runtime before the call returns)
-  if (failed(sc.alloc((void**)&d_chunks, chunks.size() * 8), "chunk list") ||
-      failed(sc.alloc((void**)&d_prog, image.size() * sizeof(Ins)), "program") ||
-      failed(sc.alloc((void**)&st, sizeof(YrState)), "state") || failed(sc.alloc((void**)&f.y.keep, n), "keep flags") ||
-      failed(sc.alloc((void**)&f.dense, n * 4), "dense ids") || failed(sc.alloc((void**)&ccount, (size_t)nchunks * 4), "chunk counts") ||
-      failed(sc.alloc((void**)&cbase, (size_t)nchunks * 4), "chunk bases") ||
-      failed(hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * 8, hipMemcpyHostToDevice, stream), "chunk upload") ||
-      (!image.empty() &&
-       failed(hipMemcpyAsync(d_prog, image.data(), image.size() * sizeof(Ins), hipMemcpyHostToDevice, stream), "program upload")) ||
-      failed(hipMemsetAsync(st, 0, sizeof(YrState), stream), "state clear") || failed(hipStreamSynchronize(stream), "uploads"))
-    return code();
-
-  YrArgs& a = f.y;
-  a.chunk = d_chunks;
-  a.nchunks = nchunks;
-  a.cols = (const int64_t* const*)inw->d_row_cols;
-  a.prog = d_prog;
-  a.code_len = (int)yp.code.size();
-  a.where_len = 0;
-  a.where_reg = -1;
+  if (ch.upload(cs, sc, stream, segs, 0, n) || cs.failed(sc.alloc((void**)&a.keep, n), "keep flags") ||
+      cs.failed(sc.alloc((void**)&f.dense, n * 4), "dense ids") || cs.failed(sc.alloc((void**)&ccount, (size_t)ch.n * 4), "chunk counts") ||
+      cs.failed(sc.alloc((void**)&cbase, (size_t)ch.n * 4), "chunk bases") || yr_setup(cs, sc, stream, yp, ch, inw, &a, &st))
+    return cs.code(err);
   a.ccount = ccount;
   a.cbase = cbase;
-  a.err = &st->err;
-  a.ncols = yp.ncols;
-  for (int c = 0; c < yp.ncols; ++c) {
-    a.yield_reg[c] = yp.yield_reg[c];
-    a.yield_const[c] = yp.yield_const[c];
-  }
-  a.str = yp.str;
-  a.now_sec = yp.now_sec;
-  a.rand_seed = yp.rand_seed;
   f.vid_col = plan.vid_col;
   f.vids = plan.vids;
   f.nv = plan.nv;
@@ -133,14 +81,14 @@ int32_t ws_fetch_vertices(Workspace* inw, const int64_t* host_vids, hipStream_t 
 
   // ---- the join, the ranks
   tm.begin();
-  he = launch_fv_resolve(f, grid, stream);
+  hipError_t he = launch_fv_resolve(f, ch.grid, stream);
   tm.end(FV_K_RESOLVE, (double)n * (8.0 + 4.0 + 1.0));
-  if (failed(he, "k_fv_resolve")) return code();
-  he = launch_yr_scan(ccount, nchunks, cbase, st, stream);
+  if (cs.failed(he, "k_fv_resolve")) return cs.code(err);
+  he = launch_yr_scan(ccount, ch.n, cbase, st, stream);
   YrState got{};
-  if (failed(he, "k_yr_scan") || failed(hipMemcpyAsync(&got, st, sizeof(YrState), hipMemcpyDeviceToHost, stream), "found rows read") ||
-      failed(hipStreamSynchronize(stream), "join"))
-    return code();
+  if (cs.failed(he, "k_yr_scan") || cs.failed(hipMemcpyAsync(&got, st, sizeof(YrState), hipMemcpyDeviceToHost, stream), "found rows read") ||
+      cs.failed(hipStreamSynchronize(stream), "join"))
+    return cs.code(err);
   const uint64_t nout = got.total;
   if (nout > n) {
     if (err) *err = "FETCH: " + std::to_string(nout) + " rows found of " + std::to_string(n);
@@ -149,21 +97,20 @@ int32_t ws_fetch_vertices(Workspace* inw, const int64_t* host_vids, hipStream_t 
   if (!nout) return NBG_OK;
 
   // ---- the YIELDs of the found rows
-  if (failed(new_rows(res, nout, yp.ncols), "result rows")) return code();
+  if (cs.failed(res.reserve(stream, nout, yp.ncols), "result rows")) return cs.code(err);
   for (int c = 0; c < yp.ncols; ++c) a.out[c] = ws_row_col(res.w, c);
   a.cap = nout;
   tm.begin();
-  he = launch_fv_emit(f, yp.nregs, grid, stream);
+  he = launch_fv_emit(f, yp.nregs, ch.grid, stream);
   tm.end(FV_K_EMIT, (double)n * 1.0 + (double)nout * (4.0 + 8.0 * (plan.tag_cols + yp.ncols)));
-  if (failed(he, "k_fv_emit") || failed(hipMemcpyAsync(&got, st, sizeof(YrState), hipMemcpyDeviceToHost, stream), "error word read") ||
-      failed(hipStreamSynchronize(stream), "emission"))
-    return code();
+  if (cs.failed(he, "k_fv_emit") || cs.failed(hipMemcpyAsync(&got, st, sizeof(YrState), hipMemcpyDeviceToHost, stream), "error word read") ||
+      cs.failed(hipStreamSynchronize(stream), "emission"))
+    return cs.code(err);
   if (got.err) {
     if (err) *err = "FETCH: an evaluation error in a YIELD column";
     return NBG_E_EXECUTION_ERROR;
   }
-  *outw = res.w;
-  res.w = nullptr;
+  *outw = res.release();
   *rows = nout;
   return NBG_OK;
 }

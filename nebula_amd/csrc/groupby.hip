@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "ordimg.h"
+#include "stage.h"
 #include "ws.h"
 
 namespace nbg {
@@ -302,38 +303,13 @@ __global__ void __launch_bounds__(BLOCK) k_gb_emit(const GbPlan* __restrict__ pl
   }
 }
 
-// scratch of one call, released when it returns
-struct GbScratch {
-  std::vector<void*> ptrs;
-  hipError_t alloc(void** p, size_t bytes) {
-    *p = nullptr;
-    const hipError_t e = hipMalloc(p, bytes ? bytes : 8);
-    if (e == hipSuccess) ptrs.push_back(*p);
-    else (void)hipGetLastError();
-    return e;
-  }
-  ~GbScratch() {
-    for (void* p : ptrs) (void)hipFree(p);
-  }
-};
-
 }  // namespace
 
 int32_t ws_group_by(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
                     const GbPlan& plan, Workspace** outw, uint64_t* groups, std::string* err) {
   *outw = nullptr;
   *groups = 0;
-  hipError_t he = hipSuccess;
-  const char* what = "";
-  auto failed = [&](hipError_t e, const char* w) {
-    he = e;
-    what = w;
-    return e != hipSuccess;
-  };
-  auto code = [&]() -> int32_t {
-    if (err) *err = std::string("group by: ") + what + ": " + hipGetErrorString(he);
-    return he == hipErrorOutOfMemory ? NBG_E_OUT_OF_MEMORY : NBG_E_DEVICE;
-  };
+  StageStatus cs("group by");
   std::vector<uint64_t> meta;
   uint64_t total = 0;
   for (auto& sg : segs) {
@@ -355,34 +331,34 @@ int32_t ws_group_by(Workspace* inw, hipStream_t stream, const std::vector<std::p
     any_distinct = any_distinct || plan.acc[a].op == GB_DISTINCT;
   }
 
-  GbScratch sc;
+  StageScratch sc;
   uint64_t* d_meta = nullptr;
   GbPlan* d_plan = nullptr;
   unsigned long long *tab = nullptr, *counter = nullptr, *acc = nullptr, *dtab = nullptr;
   uint32_t* gidtab = nullptr;
-  if (failed(sc.alloc((void**)&d_meta, meta.size() * 8), "segment list") ||
-      failed(sc.alloc((void**)&d_plan, sizeof(GbPlan)), "plan") ||
-      failed(sc.alloc((void**)&counter, 8), "group counter"))
-    return code();
-  if (failed(hipMemcpyAsync(d_meta, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, stream), "segment upload") ||
-      failed(hipMemcpyAsync(d_plan, &plan, sizeof(GbPlan), hipMemcpyHostToDevice, stream), "plan upload") ||
-      failed(hipMemsetAsync(counter, 0, 8, stream), "counter reset"))
-    return code();
+  if (cs.failed(sc.alloc((void**)&d_meta, meta.size() * 8), "segment list") ||
+      cs.failed(sc.alloc((void**)&d_plan, sizeof(GbPlan)), "plan") ||
+      cs.failed(sc.alloc((void**)&counter, 8), "group counter"))
+    return cs.code(err);
+  if (cs.failed(hipMemcpyAsync(d_meta, meta.data(), meta.size() * 8, hipMemcpyHostToDevice, stream), "segment upload") ||
+      cs.failed(hipMemcpyAsync(d_plan, &plan, sizeof(GbPlan), hipMemcpyHostToDevice, stream), "plan upload") ||
+      cs.failed(hipMemsetAsync(counter, 0, 8, stream), "counter reset"))
+    return cs.code(err);
   int64_t* const* cols = inw->d_row_cols;
 
   uint64_t G = 1;
   if (plan.nkeys) {
-    if (failed(sc.alloc((void**)&tab, tcap * 8), "group table") ||
-        failed(sc.alloc((void**)&gidtab, tcap * 4), "group ids"))
-      return code();
-    if (failed(hipMemsetAsync(tab, 0, tcap * 8, stream), "table reset")) return code();
+    if (cs.failed(sc.alloc((void**)&tab, tcap * 8), "group table") ||
+        cs.failed(sc.alloc((void**)&gidtab, tcap * 4), "group ids"))
+      return cs.code(err);
+    if (cs.failed(hipMemsetAsync(tab, 0, tcap * 8, stream), "table reset")) return cs.code(err);
     hipLaunchKernelGGL(k_gb_keys, dim3(grid), dim3(BLOCK), 0, stream, d_meta, nseg, cols, d_plan, tab, gidtab, tcap - 1,
                        counter);
-    if (failed(hipGetLastError(), "k_gb_keys")) return code();
+    if (cs.failed(hipGetLastError(), "k_gb_keys")) return cs.code(err);
     unsigned long long hg = 0;
-    if (failed(hipMemcpyAsync(&hg, counter, 8, hipMemcpyDeviceToHost, stream), "group count") ||
-        failed(hipStreamSynchronize(stream), "key pass"))
-      return code();
+    if (cs.failed(hipMemcpyAsync(&hg, counter, 8, hipMemcpyDeviceToHost, stream), "group count") ||
+        cs.failed(hipStreamSynchronize(stream), "key pass"))
+      return cs.code(err);
     G = hg;
     if (G == 0 || G > total) {
       if (err) *err = "group by: the key pass counted " + std::to_string(G) + " groups of " + std::to_string(total) + " rows";
@@ -392,15 +368,15 @@ int32_t ws_group_by(Workspace* inw, hipStream_t stream, const std::vector<std::p
       if (err) *err = "group by: 2^32 groups or more";
       return NBG_E_UNSUPPORTED;
     }
-  } else if (failed(hipStreamSynchronize(stream), "uploads")) {   // (the host buffers above are locals)
-    return code();
+  } else if (cs.failed(hipStreamSynchronize(stream), "uploads")) {   // (the host buffers above are locals)
+    return cs.code(err);
   }
 
   const uint64_t cells = (uint64_t)plan.nacc * G;
-  if (failed(sc.alloc((void**)&acc, cells * 8), "accumulators")) return code();
+  if (cs.failed(sc.alloc((void**)&acc, cells * 8), "accumulators")) return cs.code(err);
   hipLaunchKernelGGL(k_gb_init, dim3((unsigned)std::min<uint64_t>(cdiv(cells, BLOCK), 4096)), dim3(BLOCK), 0, stream,
                      d_plan, acc, G);
-  if (failed(hipGetLastError(), "k_gb_init")) return code();
+  if (cs.failed(hipGetLastError(), "k_gb_init")) return cs.code(err);
   const bool lds = cells * 8 <= GB_LDS_BYTES;
   for (int pass = 1; pass <= (any_sq ? 2 : 1); ++pass) {
     if (lds)
@@ -409,38 +385,26 @@ int32_t ws_group_by(Workspace* inw, hipStream_t stream, const std::vector<std::p
     else
       hipLaunchKernelGGL(k_gb_accum<false>, dim3(grid), dim3(BLOCK), 0, stream, d_meta, nseg, cols, d_plan, tab, gidtab,
                          tcap - 1, acc, G, pass);
-    if (failed(hipGetLastError(), "k_gb_accum")) return code();
+    if (cs.failed(hipGetLastError(), "k_gb_accum")) return cs.code(err);
   }
   if (any_distinct) {
-    if (failed(sc.alloc((void**)&dtab, tcap * 8), "COUNT_DISTINCT table")) return code();
+    if (cs.failed(sc.alloc((void**)&dtab, tcap * 8), "COUNT_DISTINCT table")) return cs.code(err);
     for (int a = 0; a < plan.nacc; ++a) {
       if (plan.acc[a].op != GB_DISTINCT) continue;
-      if (failed(hipMemsetAsync(dtab, 0, tcap * 8, stream), "COUNT_DISTINCT table reset")) return code();
+      if (cs.failed(hipMemsetAsync(dtab, 0, tcap * 8, stream), "COUNT_DISTINCT table reset")) return cs.code(err);
       hipLaunchKernelGGL(k_gb_distinct, dim3(grid), dim3(BLOCK), 0, stream, d_meta, nseg, cols, d_plan, tab, gidtab,
                          tcap - 1, a, dtab, tcap - 1, acc, G);
-      if (failed(hipGetLastError(), "k_gb_distinct")) return code();
+      if (cs.failed(hipGetLastError(), "k_gb_distinct")) return cs.code(err);
     }
   }
 
-  // the result: a workspace holding nothing but its rows (what the row accessors read)
-  auto* w = new Workspace();
-  w->stream = stream;
-  he = hipMalloc((void**)&w->d_row_cols, MAX_YIELDS * sizeof(int64_t*));
-  if (he == hipSuccess) he = ws_reserve_rows(w, G, plan.nout);
-  if (he != hipSuccess) {
-    (void)hipGetLastError();
-    ws_destroy(w);
-    what = "result rows";
-    return code();
-  }
+  RowsWs res;
+  if (cs.failed(res.reserve(stream, G, plan.nout), "result rows")) return cs.code(err);
   const uint64_t tslots = plan.nkeys ? tcap : 1;
   hipLaunchKernelGGL(k_gb_emit, dim3((unsigned)std::min<uint64_t>(cdiv(tslots, BLOCK), 8192)), dim3(BLOCK), 0, stream,
-                     d_plan, tab, gidtab, tslots, cols, acc, G, (int64_t* const*)w->d_row_cols);
-  if (failed(hipGetLastError(), "k_gb_emit") || failed(hipStreamSynchronize(stream), "aggregation")) {
-    ws_destroy(w);
-    return code();
-  }
-  *outw = w;
+                     d_plan, tab, gidtab, tslots, cols, acc, G, (int64_t* const*)res.w->d_row_cols);
+  if (cs.failed(hipGetLastError(), "k_gb_emit") || cs.failed(hipStreamSynchronize(stream), "aggregation")) return cs.code(err);
+  *outw = res.release();
   *groups = G;
   return NBG_OK;
 }

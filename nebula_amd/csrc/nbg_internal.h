@@ -709,6 +709,30 @@ hipError_t ws_distinct(Workspace* w, const std::vector<std::array<uint64_t, 3>>&
                        const std::vector<std::vector<VKind>>& kinds, std::vector<uint32_t>* counts);
 const uint32_t* ws_current_frontier(Workspace* w);
 
+// ---- what the stages over device rows share (their drivers' frame is stage.h)
+// A rows-only result workspace (what the row accessors read), destroyed unless released.
+struct RowsWs {
+  Workspace* w = nullptr;
+  // a fresh workspace on `stream` with room for rows x ncols; clears the sticky error on failure
+  hipError_t reserve(hipStream_t stream, uint64_t rows, int ncols);   // (stage.h: the .hip files)
+  Workspace* release() {
+    Workspace* r = w;
+    w = nullptr;
+    return r;
+  }
+  ~RowsWs() {
+    if (w) ws_destroy(w);
+  }
+};
+// a stage's nbg_profile_read entries, timed while nbg_profile mode 1 is on (StageTimer, stage.h)
+template <int KINDS>
+struct StageProf {
+  bool on = false;
+  uint64_t launches[KINDS] = {};
+  double ms[KINDS] = {};
+  double bytes[KINDS] = {};
+};
+
 // ---- GROUP BY over device rows (groupby.hip; GroupByExecutor.cpp:226-322, AggregateFunction.h)
 // The request compiled to accumulator slots (one 8-byte cell per group each; slot 0 is always
 // the group's row count) and to one emit rule per result column.
@@ -780,18 +804,12 @@ constexpr uint64_t OB_CHUNK = 2048;   // rows a workgroup walks per chunk of a s
 enum ObKernel { OB_K_IOTA = 0, OB_K_HIST, OB_K_PICK, OB_K_COMPACT, OB_K_IMAGE, OB_K_SORT, OB_K_GATHER, OB_K_COPY,
                 OB_KINDS };
 extern const char* const kObKernelNames[OB_KINDS];
-struct ObProf {
-  bool on = false;
-  uint64_t launches[OB_KINDS] = {};
-  double ms[OB_KINDS] = {};
-  double bytes[OB_KINDS] = {};
-};
 // Orders the rows of `inw` listed by segs (first row, rows) and writes rows [lo, hi) of that order
 // into a fresh rows-only workspace on `stream` (*outw; ws_destroy releases it).  Synchronous;
 // every scratch allocation is released before it returns.  NBG_OK, NBG_E_OUT_OF_MEMORY or
 // NBG_E_DEVICE (*err names the failing call).
 int32_t ws_order_by(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
-                    const ObPlan& plan, Workspace** outw, ObProf* prof, std::string* err);
+                    const ObPlan& plan, Workspace** outw, StageProf<OB_KINDS>* prof, std::string* err);
 
 // ---- UNION / INTERSECT / MINUS over device rows (setops.hip; SetExecutor.cpp:98-383).  The
 // request planned per column: how two cells compare and what casts a right cell to the left's type.
@@ -815,12 +833,6 @@ constexpr uint64_t SO_MIN_SLOTS = 1024;   // the row table: 2 x inserted rows, a
 // nbg_profile_read's set-operation entries (kSoKernelNames), timed while nbg_profile mode 1 is on
 enum SoKernel { SO_K_INSERT = 0, SO_K_PROBE, SO_K_EMIT, SO_K_COPY, SO_KINDS };
 extern const char* const kSoKernelNames[SO_KINDS];
-struct SoProf {
-  bool on = false;
-  uint64_t launches[SO_KINDS] = {};
-  double ms[SO_KINDS] = {};
-  double bytes[SO_KINDS] = {};
-};
 // Combines the rows of `lw` listed by lsegs with those of `rw` listed by rsegs (first row, rows)
 // into a fresh rows-only workspace on `stream` (*outw; nullptr when the result has no rows) of
 // *rows rows.  Synchronous; every scratch allocation is released before it returns.  NBG_OK,
@@ -829,7 +841,7 @@ struct SoProf {
 int32_t ws_set_op(Workspace* lw, Workspace* rw, hipStream_t stream,
                   const std::vector<std::pair<uint64_t, uint64_t>>& lsegs,
                   const std::vector<std::pair<uint64_t, uint64_t>>& rsegs, const SoPlan& plan, Workspace** outw,
-                  uint64_t* rows, SoProf* prof, std::string* err);
+                  uint64_t* rows, StageProf<SO_KINDS>* prof, std::string* err);
 
 // ---- YIELD ... WHERE over device rows (yieldrows.hip; YieldExecutor.cpp:178-282).  One program
 // compiled in CompileEnv's rows mode (WHERE first, then the YIELDs) and run per row.
@@ -851,12 +863,6 @@ struct YrPlan {
 // nbg_profile_read's YIELD entries (kYrKernelNames), timed while nbg_profile mode 1 is on
 enum YrKernel { YR_K_FILTER = 0, YR_K_SCAN, YR_K_EMIT, YR_KINDS };
 extern const char* const kYrKernelNames[YR_KINDS];
-struct YrProf {
-  bool on = false;
-  uint64_t launches[YR_KINDS] = {};
-  double ms[YR_KINDS] = {};
-  double bytes[YR_KINDS] = {};
-};
 // The row kernels sit beside the interpreter (kernels.hip); yieldrows.hip drives them.
 // chunk: stage_chunks' list on the device; cols: the input's column bases (device array).
 struct YrArgs {
@@ -891,7 +897,7 @@ hipError_t launch_yr_emit(const YrArgs& a, int nregs, unsigned grid, hipStream_t
 // Synchronous; every scratch allocation is released before it returns.  NBG_OK,
 // NBG_E_EXECUTION_ERROR (an evaluation error), NBG_E_OUT_OF_MEMORY or NBG_E_DEVICE.
 int32_t ws_yield_rows(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
-                      const YrPlan& plan, Workspace** outw, uint64_t* rows, YrProf* prof, std::string* err);
+                      const YrPlan& plan, Workspace** outw, uint64_t* rows, StageProf<YR_KINDS>* prof, std::string* err);
 
 // ---- FETCH PROP ON <tag> over device rows (fetchrows.hip; FetchVerticesExecutor.cpp:19-311).  The
 // vid column is joined to the dense vertex ids (k_fv_resolve), the found rows are ranked
@@ -912,12 +918,6 @@ struct FvPlan {
 };
 enum FvKernel { FV_K_RESOLVE = 0, FV_K_EMIT, FV_KINDS };   // (the scan between them is k_yr_scan, untimed here)
 extern const char* const kFvKernelNames[FV_KINDS];
-struct FvProf {
-  bool on = false;
-  uint64_t launches[FV_KINDS] = {};
-  double ms[FV_KINDS] = {};
-  double bytes[FV_KINDS] = {};
-};
 struct FvArgs {
   YrArgs y;                         // keep / ccount / cbase always set; cols: the input's column bases
   int vid_col;
@@ -938,7 +938,7 @@ hipError_t launch_fv_emit(const FvArgs& a, int nregs, unsigned grid, hipStream_t
 // rows, in the input's order.  Synchronous; every scratch allocation is released before it
 // returns.  NBG_OK, NBG_E_EXECUTION_ERROR (an evaluation error), NBG_E_OUT_OF_MEMORY or NBG_E_DEVICE.
 int32_t ws_fetch_vertices(Workspace* inw, const int64_t* host_vids, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
-                          const FvPlan& plan, Workspace** outw, uint64_t* rows, FvProf* prof, std::string* err);
+                          const FvPlan& plan, Workspace** outw, uint64_t* rows, StageProf<FV_KINDS>* prof, std::string* err);
 
 // Query pipeline (all asynchronous on the workspace stream until ws_end_query):
 hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, const std::vector<TypeProgram>* progs,

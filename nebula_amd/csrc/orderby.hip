@@ -200,31 +200,14 @@ __global__ void __launch_bounds__(BLOCK) k_ob_copy(const uint64_t* __restrict__ 
   }
 }
 
-using ObScratch = StageScratch;
-using ObTimer = StageTimer<ObProf>;
-
-std::vector<uint64_t> ob_chunks(const std::vector<std::pair<uint64_t, uint64_t>>& segs, uint64_t lo, uint64_t hi) {
-  return stage_chunks(segs, lo, hi);
-}
-
 unsigned ob_flat_grid(uint64_t n) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>(cdiv(n, BLOCK), 1), OB_GRID); }
 
 }  // namespace
 
 int32_t ws_order_by(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
-                    const ObPlan& plan, Workspace** outw, ObProf* prof, std::string* err) {
+                    const ObPlan& plan, Workspace** outw, StageProf<OB_KINDS>* prof, std::string* err) {
   *outw = nullptr;
-  hipError_t he = hipSuccess;
-  const char* what = "";
-  auto failed = [&](hipError_t e, const char* w) {
-    he = e;
-    what = w;
-    return e != hipSuccess;
-  };
-  auto code = [&]() -> int32_t {
-    if (err) *err = std::string("order by: ") + what + ": " + hipGetErrorString(he);
-    return he == hipErrorOutOfMemory ? NBG_E_OUT_OF_MEMORY : NBG_E_DEVICE;
-  };
+  StageStatus cs("order by");
   uint64_t total = 0;
   for (auto& sg : segs) total += sg.second;
   if (plan.lo >= plan.hi || plan.hi > total || plan.nf < 0 || plan.nf > MAX_YIELDS || plan.ncols < 1 ||
@@ -235,38 +218,21 @@ int32_t ws_order_by(Workspace* inw, hipStream_t stream, const std::vector<std::p
   const uint64_t nout = plan.hi - plan.lo;
   int64_t* const* cols = inw->d_row_cols;
 
-  // the result: a workspace holding nothing but its rows (what the row accessors read)
-  struct WsGuard {
-    Workspace* w = nullptr;
-    ~WsGuard() { if (w) ws_destroy(w); }
-  } res;
-  res.w = new Workspace();
-  res.w->stream = stream;
-  he = hipMalloc((void**)&res.w->d_row_cols, MAX_YIELDS * sizeof(int64_t*));
-  if (he == hipSuccess) he = ws_reserve_rows(res.w, nout, plan.ncols);
-  if (he != hipSuccess) {
-    (void)hipGetLastError();
-    what = "result rows";
-    return code();
-  }
+  RowsWs res;
+  if (cs.failed(res.reserve(stream, nout, plan.ncols), "result rows")) return cs.code(err);
   int64_t* const* ocols = (int64_t* const*)res.w->d_row_cols;
 
-  ObScratch sc;      // (declared before the timer: the timer's events are resolved first)
-  ObTimer tm{prof, stream, {}, nullptr};
+  StageScratch sc;      // (declared before the timer: the timer's events are resolved first)
+  StageTimer<OB_KINDS> tm{prof, stream, {}, nullptr};
   // the chunks the kernels walk: the window's slices (LIMIT only), else every row
-  const std::vector<uint64_t> chunks = plan.nf ? ob_chunks(segs, 0, total) : ob_chunks(segs, plan.lo, plan.hi);
-  const uint32_t nchunks = (uint32_t)(chunks.size() / 3);
-  const unsigned cgrid = std::min<unsigned>(std::max<uint32_t>(nchunks, 1), OB_GRID);
-  uint64_t* d_chunks = nullptr;
-  if (failed(sc.alloc((void**)&d_chunks, chunks.size() * 8), "chunk list") ||
-      failed(hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * 8, hipMemcpyHostToDevice, stream), "chunk upload"))
-    return code();
+  StageChunks ch;
+  if (ch.upload(cs, sc, stream, segs, plan.nf ? 0 : plan.lo, plan.nf ? total : plan.hi)) return cs.code(err);
 
   if (!plan.nf) {
     tm.begin();
-    hipLaunchKernelGGL(k_ob_copy, dim3(cgrid), dim3(BLOCK), 0, stream, d_chunks, nchunks, cols, plan.ncols, ocols);
+    hipLaunchKernelGGL(k_ob_copy, dim3(ch.grid), dim3(BLOCK), 0, stream, ch.dev, ch.n, cols, plan.ncols, ocols);
     tm.end(OB_K_COPY, (double)nout * plan.ncols * 16.0);
-    if (failed(hipGetLastError(), "k_ob_copy") || failed(hipStreamSynchronize(stream), "copy")) return code();
+    if (cs.failed(hipGetLastError(), "k_ob_copy") || cs.failed(hipStreamSynchronize(stream), "copy")) return cs.code(err);
     *outw = res.w;
     res.w = nullptr;
     return NBG_OK;
@@ -274,9 +240,9 @@ int32_t ws_order_by(Workspace* inw, hipStream_t stream, const std::vector<std::p
 
   auto flags_of = [&](int f) { return (plan.dbl[f] ? OB_DBL : 0u) | (plan.desc[f] ? OB_DESC : 0u); };
   std::vector<const int64_t*> hcols(plan.ncols);   // the columns' bases (the kernels here read one column each)
-  if (failed(hipMemcpyAsync(hcols.data(), cols, plan.ncols * sizeof(int64_t*), hipMemcpyDeviceToHost, stream), "column bases") ||
-      failed(hipStreamSynchronize(stream), "column bases"))
-    return code();
+  if (cs.failed(hipMemcpyAsync(hcols.data(), cols, plan.ncols * sizeof(int64_t*), hipMemcpyDeviceToHost, stream), "column bases") ||
+      cs.failed(hipStreamSynchronize(stream), "column bases"))
+    return cs.code(err);
   // ---- the rows to sort: every row, or the candidates of the first-K selection
   uint64_t n = total;
   uint64_t* rows_a = nullptr;
@@ -286,78 +252,77 @@ int32_t ws_order_by(Workspace* inw, hipStream_t stream, const std::vector<std::p
     ObSel* st = nullptr;
     ObSel init{};
     init.k = plan.hi - 1;   // the K-th smallest image, 0-based
-    if (failed(sc.alloc((void**)&st, sizeof(ObSel)), "selection state") ||
-        failed(hipMemcpyAsync(st, &init, sizeof(ObSel), hipMemcpyHostToDevice, stream), "selection state upload"))
-      return code();
+    if (cs.failed(sc.alloc((void**)&st, sizeof(ObSel)), "selection state") ||
+        cs.failed(hipMemcpyAsync(st, &init, sizeof(ObSel), hipMemcpyHostToDevice, stream), "selection state upload"))
+      return cs.code(err);
     for (int shift = 56; shift >= 0; shift -= 8) {
       tm.begin();
-      hipLaunchKernelGGL(k_ob_hist, dim3(cgrid), dim3(BLOCK), 0, stream, d_chunks, nchunks, col0, flags_of(0), shift, st);
+      hipLaunchKernelGGL(k_ob_hist, dim3(ch.grid), dim3(BLOCK), 0, stream, ch.dev, ch.n, col0, flags_of(0), shift, st);
       tm.end(OB_K_HIST, (double)total * 8.0);
-      if (failed(hipGetLastError(), "k_ob_hist")) return code();
+      if (cs.failed(hipGetLastError(), "k_ob_hist")) return cs.code(err);
       tm.begin();
       hipLaunchKernelGGL(k_ob_pick, dim3(1), dim3(256), 0, stream, st, shift);
       tm.end(OB_K_PICK, 256.0 * 16.0);
-      if (failed(hipGetLastError(), "k_ob_pick")) return code();
+      if (cs.failed(hipGetLastError(), "k_ob_pick")) return cs.code(err);
     }
     ObSel got{};
-    if (failed(hipMemcpyAsync(&got, st, sizeof(ObSel), hipMemcpyDeviceToHost, stream), "selection read") ||
-        failed(hipStreamSynchronize(stream), "selection"))
-      return code();
+    if (cs.failed(hipMemcpyAsync(&got, st, sizeof(ObSel), hipMemcpyDeviceToHost, stream), "selection read") ||
+        cs.failed(hipStreamSynchronize(stream), "selection"))
+      return cs.code(err);
     n = got.below + got.equal;   // every row at or below the K-th image
     if (n < plan.hi || n > total || got.k >= got.equal) {
       if (err) *err = "order by: the selection counted " + std::to_string(n) + " candidates for K = " + std::to_string(plan.hi);
       return NBG_E_DEVICE;
     }
-    if (failed(sc.alloc((void**)&rows_a, n * 8), "candidates")) return code();
+    if (cs.failed(sc.alloc((void**)&rows_a, n * 8), "candidates")) return cs.code(err);
     tm.begin();
-    hipLaunchKernelGGL(k_ob_compact, dim3(cgrid), dim3(BLOCK), 0, stream, d_chunks, nchunks, col0, flags_of(0), st, rows_a, n);
+    hipLaunchKernelGGL(k_ob_compact, dim3(ch.grid), dim3(BLOCK), 0, stream, ch.dev, ch.n, col0, flags_of(0), st, rows_a, n);
     tm.end(OB_K_COMPACT, (double)total * 8.0 + (double)n * 8.0);
     unsigned long long ncand = 0;
-    if (failed(hipGetLastError(), "k_ob_compact") ||
-        failed(hipMemcpyAsync(&ncand, &st->ncand, 8, hipMemcpyDeviceToHost, stream), "candidate count") ||
-        failed(hipStreamSynchronize(stream), "compaction"))
-      return code();
+    if (cs.failed(hipGetLastError(), "k_ob_compact") ||
+        cs.failed(hipMemcpyAsync(&ncand, &st->ncand, 8, hipMemcpyDeviceToHost, stream), "candidate count") ||
+        cs.failed(hipStreamSynchronize(stream), "compaction"))
+      return cs.code(err);
     if (ncand != n) {
       if (err) *err = "order by: " + std::to_string(ncand) + " candidates compacted, " + std::to_string(n) + " counted";
       return NBG_E_DEVICE;
     }
   } else {
-    if (failed(sc.alloc((void**)&rows_a, n * 8), "permutation")) return code();
+    if (cs.failed(sc.alloc((void**)&rows_a, n * 8), "permutation")) return cs.code(err);
     tm.begin();
-    hipLaunchKernelGGL(k_ob_iota, dim3(cgrid), dim3(BLOCK), 0, stream, d_chunks, nchunks, rows_a);
+    hipLaunchKernelGGL(k_ob_iota, dim3(ch.grid), dim3(BLOCK), 0, stream, ch.dev, ch.n, rows_a);
     tm.end(OB_K_IOTA, (double)n * 8.0);
-    if (failed(hipGetLastError(), "k_ob_iota")) return code();
+    if (cs.failed(hipGetLastError(), "k_ob_iota")) return cs.code(err);
   }
 
   // ---- stable LSD passes over the factors, last first
   uint64_t *rows_b = nullptr, *keys_a = nullptr, *keys_b = nullptr;
   void* tmp = nullptr;
-  if (failed(sc.alloc((void**)&rows_b, n * 8), "permutation buffer") ||
-      failed(sc.alloc((void**)&keys_a, n * 8), "sort keys") || failed(sc.alloc((void**)&keys_b, n * 8), "sort keys"))
-    return code();
+  if (cs.failed(sc.alloc((void**)&rows_b, n * 8), "permutation buffer") ||
+      cs.failed(sc.alloc((void**)&keys_a, n * 8), "sort keys") || cs.failed(sc.alloc((void**)&keys_b, n * 8), "sort keys"))
+    return cs.code(err);
   rocprim::double_buffer<uint64_t> keys(keys_a, keys_b), perm(rows_a, rows_b);
   size_t tmp_bytes = 0;
-  if (failed(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, perm, (size_t)n, 0u, 64u, stream), "sort sizing") ||
-      failed(sc.alloc(&tmp, tmp_bytes), "sort scratch"))
-    return code();
+  if (cs.failed(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, perm, (size_t)n, 0u, 64u, stream), "sort sizing") ||
+      cs.failed(sc.alloc(&tmp, tmp_bytes), "sort scratch"))
+    return cs.code(err);
   for (int f = plan.nf - 1; f >= 0; --f) {
     tm.begin();
     hipLaunchKernelGGL(k_ob_image, dim3(ob_flat_grid(n)), dim3(BLOCK), 0, stream, perm.current(), n, hcols[plan.col[f]],
                        flags_of(f), keys.current());
     tm.end(OB_K_IMAGE, (double)n * 24.0);
-    if (failed(hipGetLastError(), "k_ob_image")) return code();
+    if (cs.failed(hipGetLastError(), "k_ob_image")) return cs.code(err);
     tm.begin();
     const hipError_t se = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, perm, (size_t)n, 0u, 64u, stream);
     tm.end(OB_K_SORT, (double)n * 32.0);
-    if (failed(se, "radix_sort_pairs")) return code();
+    if (cs.failed(se, "radix_sort_pairs")) return cs.code(err);
   }
   tm.begin();
   hipLaunchKernelGGL(k_ob_gather, dim3(ob_flat_grid(nout)), dim3(BLOCK), 0, stream, perm.current() + plan.lo, nout, cols,
                      plan.ncols, ocols);
   tm.end(OB_K_GATHER, (double)nout * (8.0 + plan.ncols * 16.0));
-  if (failed(hipGetLastError(), "k_ob_gather") || failed(hipStreamSynchronize(stream), "ordering")) return code();
-  *outw = res.w;
-  res.w = nullptr;
+  if (cs.failed(hipGetLastError(), "k_ob_gather") || cs.failed(hipStreamSynchronize(stream), "ordering")) return cs.code(err);
+  *outw = res.release();
   return NBG_OK;
 }
 

@@ -1,10 +1,14 @@
-// nebula_amd — what the stages over device-resident rows share (orderby.hip, setops.hip): the
-// chunk list that spreads an input's segments over the device, the scratch of one call, and the
-// event pairs nbg_profile puts around each launch.
+// nebula_amd — the frame of a driver of a stage over device-resident rows (groupby.hip, orderby.hip,
+// setops.hip, yieldrows.hip, fetchrows.hip): the status of its HIP calls, its result workspace
+// (RowsWs, nbg_internal.h), the scratch of one call, the event pairs nbg_profile puts around each
+// launch, the chunk list that spreads an input's segments over the device, and the YrPlan setup
+// YIELD and FETCH share.  A driver declares its scratch before its timer: the timer's events are
+// resolved first.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -16,6 +20,33 @@ constexpr unsigned STAGE_GRID = 2048;   // 8 workgroups per CU; the chunks beyon
 
 __device__ __forceinline__ uint32_t lane_rank(unsigned long long bal) {   // set bits below this lane
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+}
+
+// what a driver's HIP calls came to: `failed` records and tests one, `code` reports the last
+struct StageStatus {
+  const char* prefix;   // "order by", "YIELD", ...: what the message opens with
+  hipError_t he = hipSuccess;
+  const char* what = "";
+  explicit StageStatus(const char* p) : prefix(p) {}
+  bool failed(hipError_t e, const char* w) {
+    he = e;
+    what = w;
+    return e != hipSuccess;
+  }
+  int32_t code(std::string* err) const {
+    if (err) *err = std::string(prefix) + ": " + what + ": " + hipGetErrorString(he);
+    return he == hipErrorOutOfMemory ? NBG_E_OUT_OF_MEMORY : NBG_E_DEVICE;
+  }
+};
+
+// the result: a workspace holding nothing but its rows (what the row accessors read)
+inline hipError_t RowsWs::reserve(hipStream_t stream, uint64_t rows, int ncols) {
+  w = new Workspace();
+  w->stream = stream;
+  hipError_t e = hipMalloc((void**)&w->d_row_cols, MAX_YIELDS * sizeof(int64_t*));
+  if (e == hipSuccess) e = ws_reserve_rows(w, rows, ncols);
+  if (e != hipSuccess) (void)hipGetLastError();
+  return e;
 }
 
 // scratch of one call, released when it returns
@@ -34,10 +65,10 @@ struct StageScratch {
 };
 
 // an event pair around each launch while nbg_profile is on, resolved after the call's last wait;
-// Prof: { bool on; uint64_t launches[]; double ms[]; double bytes[]; }
-template <class Prof>
+// a StageProf of the stage's kinds
+template <int KINDS>
 struct StageTimer {
-  Prof* prof;
+  StageProf<KINDS>* prof;
   hipStream_t stream;
   struct Rec { int kind; hipEvent_t a, b; double bytes; };
   std::vector<Rec> recs;
@@ -87,6 +118,57 @@ inline std::vector<uint64_t> stage_chunks(const std::vector<std::pair<uint64_t, 
     at += sg.second;
   }
   return out;
+}
+
+// stage_chunks on the device.  The host copy lives as long as the object, so the upload needs no
+// wait of its own.
+struct StageChunks {
+  std::vector<uint64_t> host;
+  uint64_t* dev = nullptr;
+  uint32_t n = 0;
+  unsigned grid = 1;   // one workgroup per chunk, at most STAGE_GRID
+  bool upload(StageStatus& st, StageScratch& sc, hipStream_t stream,
+              const std::vector<std::pair<uint64_t, uint64_t>>& segs, uint64_t lo, uint64_t hi) {
+    host = stage_chunks(segs, lo, hi);
+    n = (uint32_t)(host.size() / 3);
+    grid = std::min<unsigned>(std::max<uint32_t>(n, 1), STAGE_GRID);
+    return st.failed(sc.alloc((void**)&dev, host.size() * 8), "chunk list") ||
+           st.failed(hipMemcpyAsync(dev, host.data(), host.size() * 8, hipMemcpyHostToDevice, stream), "chunk upload");
+  }
+};
+
+// What YIELD and FETCH make of a YrPlan before their first launch: the program image on the device
+// (code, then data), a cleared YrState, and the members of YrArgs the plan, the chunks and the
+// input decide.  Waits for the uploads (the image is a local).
+inline bool yr_setup(StageStatus& st, StageScratch& sc, hipStream_t stream, const YrPlan& plan, const StageChunks& ch,
+                     const Workspace* inw, YrArgs* a, YrState** state) {
+  std::vector<Ins> image(plan.code);
+  image.insert(image.end(), plan.data.begin(), plan.data.end());
+  Ins* d_prog = nullptr;
+  if (st.failed(sc.alloc((void**)&d_prog, image.size() * sizeof(Ins)), "program") ||
+      st.failed(sc.alloc((void**)state, sizeof(YrState)), "state") ||
+      (!image.empty() &&
+       st.failed(hipMemcpyAsync(d_prog, image.data(), image.size() * sizeof(Ins), hipMemcpyHostToDevice, stream), "program upload")) ||
+      st.failed(hipMemsetAsync(*state, 0, sizeof(YrState), stream), "state clear") ||
+      st.failed(hipStreamSynchronize(stream), "uploads"))
+    return true;
+  a->chunk = ch.dev;
+  a->nchunks = ch.n;
+  a->cols = (const int64_t* const*)inw->d_row_cols;
+  a->prog = d_prog;
+  a->code_len = (int)plan.code.size();
+  a->where_len = plan.where_len;
+  a->where_reg = plan.where_reg;
+  a->err = &(*state)->err;
+  a->ncols = plan.ncols;
+  for (int c = 0; c < plan.ncols; ++c) {
+    a->yield_reg[c] = plan.yield_reg[c];
+    a->yield_const[c] = plan.yield_const[c];
+  }
+  a->str = plan.str;
+  a->now_sec = plan.now_sec;
+  a->rand_seed = plan.rand_seed;
+  return false;
 }
 
 }  // namespace nbg

@@ -1,0 +1,1026 @@
+// The stages over device-resident rows at the C ABI (include/nbg.h): nbg_group_by, nbg_order_by,
+// nbg_set_op, nbg_yield and nbg_fetch_vertices.  Each plans its request on the host, as its
+// executor in the reference checks it, and hands the plan to its driver (groupby.hip, orderby.hip,
+// setops.hip, yieldrows.hip, fetchrows.hip).
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <ctime>
+#include <set>
+
+#include "nbg_rows.h"
+
+using namespace nbg;
+
+// ============================================================================= what the stages share
+// Small checks and steps, each called where the stage's own executor stands: the order of a
+// stage's checks is the reference's, and it decides which status wins.
+namespace {
+
+using Segs = std::vector<std::pair<uint64_t, uint64_t>>;   // (first row, rows)
+
+int32_t natural_type_of(VKind k) {
+  return k == VK_DOUBLE ? NBG_T_DOUBLE : k == VK_BOOL ? NBG_T_BOOL : k == VK_STRING ? NBG_T_STRING : NBG_T_INT;
+}
+
+nbg_rows* new_rows(Engine& E, int ncols) {
+  auto* r = new nbg_rows();
+  r->eng = &E;
+  r->ncols = ncols;
+  r->on_device = true;
+  r->kinds.emplace_back(ncols, VK_INT);
+  r->const_str.emplace_back(ncols, std::string());
+  r->col_types.assign(ncols, NBG_T_INT);
+  r->wclass.emplace_back(ncols, (uint8_t)W_ID);
+  return r;
+}
+
+// rows of another engine, then host-only rows, over every input of the stage
+int32_t guard_rows(Engine& E, const std::string& label, std::initializer_list<const nbg_rows*> rows) {
+  for (const nbg_rows* r : rows)
+    if (r->eng != &E) return E.fail(NBG_E_INVALID_ARGUMENT, label + ": the rows belong to another engine");
+  for (const nbg_rows* r : rows)
+    if (!r->on_device) return E.fail(NBG_E_INVALID_ARGUMENT, label + ": the rows are host-only (not a device result)");
+  return NBG_OK;
+}
+
+int32_t guard_partitioned(Engine& E, const std::string& label) {
+  if (!E.partitioned()) return NBG_OK;
+  return E.fail(NBG_E_UNSUPPORTED, label + " on a partitioned engine (its rows live on several ranks)");
+}
+
+int32_t copy_input_names(Engine& E, const std::string& label, const char* const* given, int nc,
+                         std::vector<std::string>* names) {
+  for (int c = 0; c < nc; ++c) {
+    if (!given[c]) return E.fail(NBG_E_INVALID_ARGUMENT, label + ": null input column name");
+    names->emplace_back(given[c]);
+  }
+  return NBG_OK;
+}
+
+// the device side of a result: its workspace and its non-empty segments, on the engine's device
+struct DeviceInput {
+  Workspace* w = nullptr;
+  Segs segs;
+};
+int32_t device_input(Engine& E, const std::string& label, const nbg_rows* in, DeviceInput* d) {
+  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+  auto* m = const_cast<nbg_rows*>(in);
+  m->build_segs();
+  for (auto& sg : m->segs)
+    if (sg.end > sg.begin) d->segs.emplace_back(sg.begin, sg.end - sg.begin);
+  d->w = in->owned_ws ? in->owned_ws : in->ws;
+  return d->w ? NBG_OK : E.fail(NBG_E_INVALID_ARGUMENT, label + ": the rows have no device workspace");
+}
+
+// a driver's output becomes the result: one segment of `n` rows in `w` (the stages' result form)
+void adopt_rows(nbg_rows* r, Workspace* w, uint64_t n, int ncols) {
+  r->ws = r->owned_ws = w;
+  r->count = n;
+  nbg_rows::TypeBlocks tb;
+  tb.region = 0;
+  tb.blk_cap = n;
+  tb.counts.assign(1, (uint32_t)n);
+  r->blocks.push_back(std::move(tb));
+  for (int c = 0; c < ncols; ++c) r->dcols.push_back(ws_row_col(w, c));
+}
+
+// What a stage knows about its input's columns, computed once per call.  What follows from it
+// (which case is an error, and its text) is each stage's own.
+struct InputCols {
+  std::vector<uint8_t> mixed;      // the OVER types give the column different kinds (its kind reads VK_INT)
+  std::vector<VKind> kind;
+  std::vector<int32_t> type;       // NBG_T_*: the result schema's if it names one, else the kind's natural type
+  std::vector<std::string> spell;  // what spells the column's string constant outside the dictionary
+  std::vector<uint8_t> respelt;    // ... differs between OVER types
+  std::vector<uint8_t> spelt;      // ... is not empty for some OVER type
+  std::vector<uint8_t> outside;    // the column can hold strings outside the dictionary: spelt, or derived strings
+  bool any_mixed = false, any_respelt = false;
+  explicit InputCols(const nbg_rows* in)
+      : mixed(in->ncols, 0), kind(in->ncols, VK_INT), type(in->ncols, NBG_T_INT), spell(in->ncols), respelt(in->ncols, 0),
+        spelt(in->ncols, 0), outside(in->ncols, 0) {
+    for (int c = 0; c < in->ncols; ++c) {
+      const int k = in->col_kind(c);
+      mixed[c] = k < 0;
+      kind[c] = k < 0 ? VK_INT : (VKind)k;
+      type[c] = c < (int)in->col_types.size() && in->col_types[c] ? in->col_types[c] : natural_type_of(kind[c]);
+      bool have = false;
+      for (auto& cs : in->const_str) {
+        if ((int)cs.size() <= c) continue;
+        respelt[c] = respelt[c] || (have && spell[c] != cs[c]);
+        spelt[c] = spelt[c] || !cs[c].empty();
+        spell[c] = cs[c];
+        have = true;
+      }
+      outside[c] = spelt[c] || !in->derived.empty();
+      any_mixed = any_mixed || mixed[c];
+      any_respelt = any_respelt || respelt[c];
+    }
+  }
+};
+
+// the environment a stage compiles expressions in; `rows`: a program run per input row (CompileEnv::rows)
+CompileEnv stage_env(Engine& E, bool rows) {
+  static const std::vector<int32_t> no_over;
+  CompileEnv cenv{};
+  cenv.etype = 0;
+  cenv.over = &no_over;
+  cenv.edges = &E.edges;
+  cenv.strings = &E.snap.strings;
+  cenv.tags = &E.tags;
+  if (!rows) return cenv;
+  cenv.max_dict_len = E.refresh_max_dict_len();
+  cenv.rows = true;
+  return cenv;
+}
+
+// one YIELD column that is not passed through as it is: its register or constant in the plan, its
+// kind, type (Collector::getSchema: the value's own, or a root cast's) and constant spelling in `res`
+int32_t compile_yield_column(Engine& E, const std::string& label, const Node& n, const CompileEnv& cenv,
+                             const ColTypeEnv& tenv, ProgramBuilder& pb, int y, YrPlan* plan, nbg_rows* res) {
+  Compiled c;
+  std::string err;
+  if (int32_t rc = compile_expr(n, cenv, pb, &c, &err, true)) return E.fail(rc, label + ": " + err);
+  plan->yield_reg[y] = c.is_const ? -1 : c.reg;
+  plan->yield_const[y] = c.is_const ? c.const_bits : 0;
+  res->kinds[0][y] = c.kind;
+  res->col_types[y] = n.kind == EK_CAST ? yield_column_type(n, tenv) : natural_type_of(c.kind);
+  if (!res->col_types[y]) res->col_types[y] = natural_type_of(c.kind);
+  if (c.is_const && c.kind == VK_STRING && (c.const_bits & 1)) res->const_str[0][y] = c.const_str;
+  return NBG_OK;
+}
+
+// the compiled program into the plan, if the device can run it
+int32_t finish_program(Engine& E, const std::string& label, const ProgramBuilder& pb, YrPlan* plan) {
+  plan->code = pb.code;
+  plan->data = pb.data;
+  plan->nregs = std::max(1, pb.max_reg);
+  for (const Ins& i : plan->code)
+    if (i.op == OP_SOUT || i.op == OP_SMAT) return E.fail(NBG_E_UNSUPPORTED, label + ": an expression that builds a string");
+  if ((int)(plan->code.size() + plan->data.size()) > MAX_PROGRAM) return E.fail(NBG_E_UNSUPPORTED, label + ": program too long");
+  if (plan->nregs > interp_max_regs())
+    return E.fail(NBG_E_UNSUPPORTED, label + ": expression too deep for the device register file (" + std::to_string(plan->nregs) +
+                                         " registers, " + std::to_string(interp_max_regs()) + " fit the LDS)");
+  return NBG_OK;
+}
+
+}  // namespace
+
+// ============================================================================= GROUP BY
+// GroupByExecutor (src/graph/GroupByExecutor.cpp:44-178 the checks, :226-322 the grouping,
+// :355-391 the result schema) over a device-resident result; the kernels are in groupby.hip.
+namespace {
+
+bool gb_only_constants(const Node& n) {   // no prop, input or variable reference anywhere
+  switch (n.kind) {
+    case EK_PRIMARY: case EK_FUNC: case EK_UNARY: case EK_CAST: case EK_ARITH: case EK_REL: case EK_LOGIC: break;
+    default: return false;
+  }
+  for (auto& k : n.kids)
+    if (!k || !gb_only_constants(*k)) return false;
+  return true;
+}
+
+bool gb_is_agg_name(std::string f) {
+  for (char& ch : f) ch = (char)toupper((unsigned char)ch);
+  for (const char* a : {"COUNT", "COUNT_DISTINCT", "SUM", "AVG", "MAX", "MIN", "STD", "BIT_AND", "BIT_OR", "BIT_XOR"})
+    if (f == a) return true;
+  return false;
+}
+
+// PrimaryExpression::toString of a constant (what a bare name in GROUP BY is compared to)
+std::string gb_primary_string(const Node& n) {
+  if (n.kind != EK_PRIMARY) return std::string("\x01");   // (never an alias)
+  switch (n.prim.index()) {
+    case 0: return std::to_string(std::get<0>(n.prim));
+    case 1: return std::to_string(std::get<1>(n.prim));
+    case 2: return std::get<2>(n.prim) ? "true" : "false";
+    default: return std::get<3>(n.prim);
+  }
+}
+
+struct GbValue {          // a YIELD operand: an input column or a constant
+  int col = -1;
+  VKind kind = VK_INT;
+  int32_t type = NBG_T_INT;
+  int64_t bits = 0;       // constant payload (strings: the dictionary code)
+  std::string text;       // constant string
+};
+
+}  // namespace
+
+extern "C" {
+
+int32_t nbg_group_by(nbg_engine* h, const nbg_rows* in, const nbg_group_request* rq, nbg_rows** out) {
+  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  if (int32_t rc = guard_rows(E, "GROUP BY", {in})) return rc;
+  if (int32_t rc = guard_partitioned(E, "GROUP BY")) return rc;
+  const int ng = rq->num_groups, ny = rq->num_yields;
+  if (!in->count) {   // GroupByExecutor::execute returns before checkAll: no check, no rows
+    *out = new_rows(E, std::max(0, std::min(ny, (int)MAX_YIELDS)));
+    return NBG_OK;
+  }
+  if ((ng > 0 && (!rq->group_exprs || !rq->group_lens)) ||
+      (ny > 0 && (!rq->yield_exprs || !rq->yield_lens || !rq->yield_funs)) || !rq->input_names)
+    return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: null argument");
+  if (ng > MAX_YIELDS || ny > MAX_YIELDS)
+    return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: more than NBG_MAX_YIELDS group or yield columns");
+  std::vector<std::string> names;
+  if (int32_t rc = copy_input_names(E, "GROUP BY", rq->input_names, in->ncols, &names)) return rc;
+  auto find_col = [&](const std::string& n) {
+    auto it = std::find(names.begin(), names.end(), n);
+    return it == names.end() ? -1 : (int)(it - names.begin());
+  };
+  auto decode = [&](const uint8_t* p, uint32_t n, std::unique_ptr<Node>* node) -> int32_t {
+    std::string err;
+    if (!p || !n) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: an empty expression");
+    *node = decode_expr(p, n, &err);
+    return *node ? NBG_OK : E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: " + err);
+  };
+  // ---- prepareYield / prepareGroup / checkAll
+  if (ny <= 0) return E.fail(NBG_E_SYNTAX_ERROR, "Yield cols is empty");
+  std::vector<std::unique_ptr<Node>> ynodes(ny), gnodes(std::max(ng, 0));
+  std::map<std::string, int> aliases;   // alias -> the first `$-.x AS alias` yield
+  for (int y = 0; y < ny; ++y) {
+    if (int32_t rc = decode(rq->yield_exprs[y], rq->yield_lens[y], &ynodes[y])) return rc;
+    const int32_t f = rq->yield_funs[y];
+    if (f < NBG_AGG_NONE || f > NBG_AGG_BIT_XOR) return E.fail(NBG_E_INVALID_ARGUMENT, "GROUP BY: unknown function");
+    const Node& n = *ynodes[y];
+    const bool star = n.kind == EK_PRIMARY && n.prim.index() == 3 && std::get<3>(n.prim) == "*";
+    if (star && f != NBG_AGG_COUNT && f != NBG_AGG_COUNT_DISTINCT) return E.fail(NBG_E_SYNTAX_ERROR, "Syntax error: near `*'");
+    const char* al = rq->yield_aliases ? rq->yield_aliases[y] : nullptr;
+    if (al && n.kind == EK_INPUT) aliases.emplace(al, y);
+  }
+  if (ng <= 0) return E.fail(NBG_E_SYNTAX_ERROR, "Group cols is empty");
+  std::set<int> key_set;          // the `$-` group keys (input columns)
+  std::vector<int> key_cols;
+  for (int g = 0; g < ng; ++g) {
+    if (int32_t rc = decode(rq->group_exprs[g], rq->group_lens[g], &gnodes[g])) return rc;
+    const Node& n = *gnodes[g];
+    if (n.kind == EK_FUNC && gb_is_agg_name(n.alias))
+      return E.fail(NBG_E_SYNTAX_ERROR, "Use invalid group function `" + n.alias + "'");
+  }
+  for (int g = 0; g < ng; ++g) {
+    const Node& n = *gnodes[g];
+    if (n.kind == EK_INPUT) {
+      const int c = find_col(n.prop);
+      if (c < 0) return E.fail(NBG_E_SYNTAX_ERROR, "Group `" + n.prop + "' isn't in output fields");
+      if (key_set.insert(c).second) key_cols.push_back(c);
+      continue;
+    }
+    if (n.kind == EK_FUNC) continue;   // (constant-folded below)
+    const std::string gname = gb_primary_string(n);
+    auto a = aliases.find(gname);
+    if (a == aliases.end()) return E.fail(NBG_E_SYNTAX_ERROR, "Group `" + gname + "' isn't in output fields");
+    const int c = find_col(ynodes[a->second]->prop);   // (absent: the yield check below answers)
+    if (c >= 0 && key_set.insert(c).second) key_cols.push_back(c);
+  }
+  for (int y = 0; y < ny; ++y) {
+    const Node& n = *ynodes[y];
+    if (n.kind == EK_INPUT) {
+      const int c = find_col(n.prop);
+      if (c < 0) return E.fail(NBG_E_SYNTAX_ERROR, "Yield `" + n.prop + "' isn't in output fields");
+      if (rq->yield_funs[y] == NBG_AGG_NONE && !key_set.count(c))
+        return E.fail(NBG_E_SYNTAX_ERROR, "Yield `" + n.prop + "' isn't in group fields");
+    } else if (n.kind == EK_VAR) {
+      return E.fail(NBG_E_SYNTAX_ERROR, "Can't support variableExpression");
+    }
+  }
+  // ---- device scope
+  if (in->misaligned || in->float_col)
+    return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  const CompileEnv cenv = stage_env(E, false);
+  const InputCols cols(in);
+  auto constant = [&](const Node& n, GbValue* v) -> int32_t {
+    if (!gb_only_constants(n)) return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: an expression that is neither `$-.col' nor constant");
+    ProgramBuilder pb;
+    Compiled c;
+    std::string err;
+    const int32_t rc = compile_expr(n, cenv, pb, &c, &err, true);
+    if (rc) return E.fail(rc, "GROUP BY: " + err);
+    if (c.always_error) return E.fail(NBG_E_EXECUTION_ERROR, "GROUP BY: a constant expression fails to evaluate");
+    if (!c.is_const || c.derived) return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: an expression that is not constant");
+    v->col = -1;
+    v->kind = c.kind;
+    v->type = natural_type_of(c.kind);
+    v->bits = c.const_bits;
+    v->text = c.const_str;
+    return NBG_OK;
+  };
+  auto column = [&](int c, GbValue* v) -> int32_t {
+    if (cols.mixed[c]) return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: column `" + names[c] + "' mixes value kinds");
+    v->col = c;
+    v->kind = cols.kind[c];
+    v->type = cols.type[c];
+    return NBG_OK;
+  };
+  for (int g = 0; g < ng; ++g) {   // a function-call key must fold: it adds nothing to the identity
+    if (gnodes[g]->kind != EK_FUNC) continue;
+    GbValue v;
+    if (int32_t rc = constant(*gnodes[g], &v)) return rc;
+  }
+  GbPlan plan;
+  plan.nkeys = (int)key_cols.size();
+  for (int k = 0; k < plan.nkeys; ++k) {
+    GbValue v;
+    if (int32_t rc = column(key_cols[k], &v)) return rc;
+    plan.key_col[k] = (int8_t)key_cols[k];
+    plan.key_dbl[k] = v.kind == VK_DOUBLE;
+  }
+  plan.acc[0] = GbAcc{GB_COUNT, 0, -1, 0, 0};
+  plan.nacc = 1;
+  plan.nout = ny;
+  std::unique_ptr<nbg_rows> res(new_rows(E, ny));
+  auto slot = [&](GbOp op, const GbValue& v, int ref) {
+    plan.acc[plan.nacc] = GbAcc{(uint8_t)op, (uint8_t)(v.kind == VK_DOUBLE), (int8_t)v.col, (uint8_t)ref, v.bits};
+    return plan.nacc++;
+  };
+  for (int y = 0; y < ny; ++y) {
+    GbValue v;
+    const Node& n = *ynodes[y];
+    if (n.kind == EK_INPUT) {
+      if (int32_t rc = column(find_col(n.prop), &v)) return rc;
+    } else if (int32_t rc = constant(n, &v)) {
+      return rc;
+    }
+    GbOut& o = plan.out[y];
+    VKind okind = VK_INT;
+    int32_t otype = NBG_T_INT;
+    auto emit_const = [&](VKind k, int32_t t, int64_t bits) {
+      o = GbOut{GE_CONST, -1, 0, bits};
+      okind = k;
+      otype = t;
+    };
+    const bool int_like = v.type == NBG_T_INT || v.type == NBG_T_VID || v.type == NBG_T_TIMESTAMP;
+    const bool is_dbl = v.type == NBG_T_DOUBLE;
+    const double zero = 0.0;
+    int64_t zero_bits;
+    memcpy(&zero_bits, &zero, 8);
+    switch (rq->yield_funs[y]) {
+      case NBG_AGG_NONE:   // Group::apply keeps the row's value: a key cell or the constant
+        if (v.col >= 0) {
+          o = GbOut{GE_KEY, (int8_t)v.col, 0, 0};
+          okind = v.kind;
+          otype = v.type;
+          if (v.kind == VK_STRING) {   // a string column the result carries over: what spells its codes outside the dictionary
+            if (cols.respelt[v.col])
+              return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: column `" + names[v.col] + "' spells different constants per OVER type");
+            res->const_str[0][y] = cols.spell[v.col];
+          }
+        } else {
+          emit_const(v.kind, v.type, v.bits);
+          res->const_str[0][y] = v.text;
+        }
+        break;
+      case NBG_AGG_COUNT:
+        o = GbOut{GE_SLOT, -1, 0, 0};
+        break;
+      case NBG_AGG_COUNT_DISTINCT:
+        if (v.col < 0) emit_const(VK_INT, NBG_T_INT, 1);
+        else o = GbOut{GE_SLOT, -1, (uint8_t)slot(GB_DISTINCT, v, 0), 0};
+        break;
+      case NBG_AGG_SUM:
+        if (int_like) {
+          o = GbOut{GE_SLOT, -1, (uint8_t)slot(GB_SUM_I, v, 0), 0};
+          otype = v.type;
+        } else if (is_dbl) {
+          o = GbOut{GE_SLOT, -1, (uint8_t)slot(GB_SUM_D, v, 0), 0};
+          okind = VK_DOUBLE;
+          otype = NBG_T_DOUBLE;
+        } else {
+          emit_const(VK_INT, NBG_T_INT, 0);
+        }
+        break;
+      case NBG_AGG_AVG:
+        okind = VK_DOUBLE;
+        otype = NBG_T_DOUBLE;
+        if (v.type == NBG_T_VID || v.type == NBG_T_TIMESTAMP)
+          return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: AVG over a VID or TIMESTAMP column");
+        if (int_like) o = GbOut{GE_AVG_I, -1, (uint8_t)slot(GB_SUM_I, v, 0), 0};
+        else if (is_dbl) o = GbOut{GE_AVG_D, -1, (uint8_t)slot(GB_SUM_D, v, 0), 0};
+        else emit_const(VK_DOUBLE, NBG_T_DOUBLE, zero_bits);
+        break;
+      case NBG_AGG_MAX: case NBG_AGG_MIN: {
+        okind = v.kind;
+        otype = v.type;
+        if (v.col < 0) {
+          emit_const(v.kind, v.type, v.bits);
+          res->const_str[0][y] = v.text;
+          break;
+        }
+        if (v.kind == VK_STRING && cols.outside[v.col])
+          return E.fail(NBG_E_UNSUPPORTED, "GROUP BY: MAX/MIN over a string column that can hold strings outside the dictionary");
+        const GbOp op = rq->yield_funs[y] == NBG_AGG_MAX ? GB_MAX : GB_MIN;
+        o = GbOut{(uint8_t)(v.kind == VK_DOUBLE ? GE_ORD_D : GE_ORD_I), -1, (uint8_t)slot(op, v, 0), 0};
+        break;
+      }
+      case NBG_AGG_STD:
+        if (v.type == NBG_T_INT || is_dbl) {
+          const int s = slot(is_dbl ? GB_SUM_D : GB_SUM_I, v, 0);
+          o = GbOut{GE_STD, -1, (uint8_t)slot(GB_SQ, v, s), 0};
+          okind = VK_DOUBLE;
+          otype = NBG_T_DOUBLE;
+        } else {
+          emit_const(VK_INT, NBG_T_INT, 0);
+        }
+        break;
+      default: {   // BIT_AND / BIT_OR / BIT_XOR: INT values only
+        if (v.type != NBG_T_INT) { emit_const(VK_INT, NBG_T_INT, 0); break; }
+        const GbOp op = rq->yield_funs[y] == NBG_AGG_BIT_AND ? GB_AND : rq->yield_funs[y] == NBG_AGG_BIT_OR ? GB_OR : GB_XOR;
+        o = GbOut{GE_SLOT, -1, (uint8_t)slot(op, v, 0), 0};
+      }
+    }
+    res->kinds[0][y] = okind;
+    res->col_types[y] = otype;
+  }
+  // ---- the passes
+  DeviceInput d;
+  if (int32_t rc = device_input(E, "GROUP BY", in, &d)) return rc;
+  Workspace* ow = nullptr;
+  uint64_t G = 0;
+  std::string err;
+  if (int32_t rc = ws_group_by(d.w, E.stream, d.segs, plan, &ow, &G, &err)) return E.fail(rc, err);
+  res->derived = in->derived;
+  adopt_rows(res.get(), ow, G, ny);
+  *out = res.release();
+  return NBG_OK;
+}
+
+// ============================================================================= ORDER BY / LIMIT
+// OrderByExecutor (src/graph/OrderByExecutor.cpp:94-155) and LimitExecutor
+// (src/graph/LimitExecutor.cpp:18-66) over a device-resident result; the kernels are in orderby.hip.
+// (under the engine lock; nbg_set_op's pass-through shortcuts are this with no factors and no LIMIT)
+static int32_t order_by_locked(Engine& E, const nbg_rows* in, const nbg_order_request* rq, nbg_rows** out) {
+  // LimitExecutor::prepare (:18-28): before anything is executed, whatever the input holds
+  if (rq->has_limit && rq->offset < 0)
+    return E.fail(NBG_E_SYNTAX_ERROR, "skip `" + std::to_string(rq->offset) + "' is illegal");
+  if (rq->has_limit && rq->count < 0)
+    return E.fail(NBG_E_SYNTAX_ERROR, "count `" + std::to_string(rq->count) + "' is illegal");
+  if (int32_t rc = guard_rows(E, "ORDER BY", {in})) return rc;
+  if (int32_t rc = guard_partitioned(E, "ORDER BY")) return rc;
+  const int nf = rq->num_factors, nc = in->ncols;
+  if (nf < 0) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: negative factor count");
+  // the result carries the input's columns: one kind and one spelling of constants per column
+  std::unique_ptr<nbg_rows> res(new_rows(E, nc));
+  res->derived = in->derived;
+  const InputCols cols(in);
+  res->kinds[0] = cols.kind;
+  res->col_types = cols.type;
+  res->const_str[0] = cols.spell;
+  if (!in->count) {   // OrderByExecutor::beforeExecute (:137-139) and LimitExecutor: no rows, no check
+    *out = res.release();
+    return NBG_OK;
+  }
+  if (!rq->input_names || (nf > 0 && (!rq->factor_names || !rq->factor_desc)))
+    return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: null argument");
+  if (nf > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: more than NBG_MAX_YIELDS factors");
+  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: the rows have no columns");
+  std::vector<std::string> names;
+  if (int32_t rc = copy_input_names(E, "ORDER BY", rq->input_names, nc, &names)) return rc;
+  ObPlan plan;
+  plan.nf = nf;
+  plan.ncols = nc;
+  for (int f = 0; f < nf; ++f) {   // getFieldIndex: the first column of that name (:140-152)
+    if (!rq->factor_names[f]) return E.fail(NBG_E_INVALID_ARGUMENT, "ORDER BY: null factor name");
+    auto it = std::find(names.begin(), names.end(), std::string(rq->factor_names[f]));
+    if (it == names.end())
+      return E.fail(NBG_E_EXECUTION_ERROR, std::string("Field (") + rq->factor_names[f] + ") not exist in input schema.");
+    plan.col[f] = (int8_t)(it - names.begin());
+    plan.desc[f] = rq->factor_desc[f] != 0;
+  }
+  // ---- device scope
+  if (in->misaligned || in->float_col)
+    return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (cols.any_mixed) return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: a column mixes value kinds between OVER types");
+  if (cols.any_respelt) return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: a string column spells different constants per OVER type");
+  for (int f = 0; f < nf; ++f) {
+    const int c = plan.col[f];
+    plan.dbl[f] = cols.kind[c] == VK_DOUBLE;
+    // dictionary codes order as their strings do (loader.cpp: the dictionary is sorted by
+    // std::string::operator<); a derived code or an out-of-dictionary constant does not
+    if (cols.kind[c] == VK_STRING && cols.outside[c])
+      return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: factor `" + names[c] + "' can hold strings outside the dictionary");
+  }
+  // ---- the window (LimitExecutor.cpp:30-66)
+  const uint64_t total = in->count;
+  plan.has_limit = rq->has_limit != 0;
+  plan.lo = 0;
+  plan.hi = total;
+  if (plan.has_limit) {
+    const uint64_t off = (uint64_t)rq->offset, cnt = (uint64_t)rq->count;
+    if (cnt == 0 || total <= off) {
+      *out = res.release();
+      return NBG_OK;
+    }
+    plan.lo = off;
+    plan.hi = cnt > total - off ? total : off + cnt;   // (off + cnt saturates)
+  }
+  if (plan.hi - plan.lo > 0xFFFFFFFFull)   // (a result segment's row count is 32 bits)
+    return E.fail(NBG_E_UNSUPPORTED, "ORDER BY: a result of 2^32 rows or more");
+  // ---- the passes
+  DeviceInput d;
+  if (int32_t rc = device_input(E, "ORDER BY", in, &d)) return rc;
+  Workspace* ow = nullptr;
+  std::string err;
+  if (int32_t rc = ws_order_by(d.w, E.stream, d.segs, plan, &ow, &E.ob_prof, &err)) return E.fail(rc, err);
+  adopt_rows(res.get(), ow, plan.hi - plan.lo, nc);
+  *out = res.release();
+  return NBG_OK;
+}
+
+int32_t nbg_order_by(nbg_engine* h, const nbg_rows* in, const nbg_order_request* rq, nbg_rows** out) {
+  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  return order_by_locked(E, in, rq, out);
+}
+
+// ============================================================================= UNION / INTERSECT / MINUS
+// SetExecutor (src/graph/SetExecutor.cpp:98-383) over two device-resident results; the kernels
+// are in setops.hip.
+int32_t nbg_set_op(nbg_engine* h, const nbg_rows* left, const nbg_rows* right, const nbg_set_request* rq,
+                   nbg_rows** out) {
+  if (!h || !left || !right || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  if (rq->op < NBG_SET_UNION || rq->op > NBG_SET_MINUS) return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: unknown operator");
+  if (int32_t rc = guard_rows(E, "set operation", {left, right})) return rc;
+  if (int32_t rc = guard_partitioned(E, "set operation")) return rc;
+  const int nc = left->ncols;
+  if (nc != right->ncols) return E.fail(NBG_E_EXECUTION_ERROR, "Field count not match.");
+  // ---- the empty-input shortcuts (SetExecutor.cpp:137-141, :163-174, :273-277, :327-337): before
+  // any schema check; a side passed on is what ORDER BY without factors and LIMIT makes of it
+  const bool uni = rq->op == NBG_SET_UNION;
+  auto as_it_is = [&](const nbg_rows* side) {
+    std::vector<const char*> names((size_t)std::max(side->ncols, 1), "");
+    nbg_order_request pass{};
+    pass.input_names = names.data();
+    return order_by_locked(E, side, &pass, out);
+  };
+  if (!left->count || !right->count) {
+    if (uni && right->count) return as_it_is(right);
+    if ((uni || rq->op == NBG_SET_MINUS) && left->count) return as_it_is(left);
+    *out = new_rows(E, nc);   // (both empty, INTERSECT with an empty side, MINUS from nothing)
+    return NBG_OK;
+  }
+  // ---- device scope, and the casts (checkSchema / doCasting, :219-262)
+  if (left->misaligned || left->float_col || right->misaligned || right->float_col)
+    return E.fail(NBG_E_UNSUPPORTED, "set operation: an input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "set operation: the rows have no columns");
+  std::unique_ptr<nbg_rows> res(new_rows(E, nc));
+  SoPlan plan;
+  plan.op = rq->op;
+  plan.distinct = uni && rq->distinct;
+  plan.ncols = nc;
+  const InputCols lcols(left), rcols(right);
+  auto int_like = [](int32_t t) { return t == NBG_T_INT || t == NBG_T_VID || t == NBG_T_TIMESTAMP; };
+  for (int c = 0; c < nc; ++c) {
+    if (lcols.mixed[c] || rcols.mixed[c])
+      return E.fail(NBG_E_UNSUPPORTED, "set operation: a column mixes value kinds between OVER types");
+    const int32_t lt = lcols.type[c], rt = rcols.type[c];
+    if ((lt == NBG_T_STRING) != (rt == NBG_T_STRING))
+      return E.fail(NBG_E_UNSUPPORTED, "set operation: column " + std::to_string(c) + " casts to or from STRING");
+    // a constant outside the dictionary has a code private to its result: nothing to compare it by
+    if (lt == NBG_T_STRING && (lcols.spelt[c] || rcols.spelt[c]))
+      return E.fail(NBG_E_UNSUPPORTED, "set operation: string column " + std::to_string(c) +
+                                           " carries a constant outside the dictionary");
+    res->kinds[0][c] = lcols.kind[c];
+    res->col_types[c] = lt;
+    plan.dbl[c] = lt == NBG_T_DOUBLE;
+    uint8_t cast = SO_KEEP;
+    if (lt != rt) {
+      if (int_like(lt)) cast = rt == NBG_T_DOUBLE ? SO_D2I : rt == NBG_T_BOOL ? SO_B2I : SO_KEEP;
+      else if (lt == NBG_T_DOUBLE) cast = rt == NBG_T_BOOL ? SO_B2D : SO_I2D;
+      else if (lt == NBG_T_BOOL) cast = rt == NBG_T_DOUBLE ? SO_D2B : SO_I2B;
+    }
+    plan.cast[c] = cast;
+  }
+  // the derived strings of both inputs (their codes are content hashes, the same in every result)
+  res->derived = left->derived;
+  for (auto& kv : right->derived) {
+    auto ins = res->derived.emplace(kv.first, kv.second);
+    if (!ins.second && ins.first->second != kv.second) return E.fail(NBG_E_EXECUTION_ERROR, "derived-string hash collision");
+  }
+  // ---- the passes
+  DeviceInput l, r;
+  if (int32_t rc = device_input(E, "set operation", left, &l)) return rc;
+  if (int32_t rc = device_input(E, "set operation", right, &r)) return rc;
+  Workspace* ow = nullptr;
+  uint64_t n = 0;
+  std::string err;
+  if (int32_t rc = ws_set_op(l.w, r.w, E.stream, l.segs, r.segs, plan, &ow, &n, &E.so_prof, &err)) return E.fail(rc, err);
+  if (ow) adopt_rows(res.get(), ow, n, nc);
+  *out = res.release();
+  return NBG_OK;
+}
+
+// ============================================================================= YIELD ... WHERE
+// YieldExecutor::executeInputs (src/graph/YieldExecutor.cpp:178-282) over a device-resident result;
+// the kernels are in yieldrows.hip and, beside the interpreter, kernels.hip.
+namespace {
+
+// what a WHERE / YIELD tree references (ExpressionContext's has*Prop and variables())
+struct YrRefs {
+  bool graph = false;                    // $^, $$ or an edge property
+  bool input = false;
+  std::set<std::string> vars;
+  std::vector<std::string> props;        // $- / $var column names, in evaluation order
+};
+void yr_refs(const Node& n, YrRefs* r) {
+  switch (n.kind) {
+    case EK_SRCPROP: case EK_DSTPROP: case EK_ALIAS: case EK_RANK: case EK_DST: case EK_SRCID: case EK_TYPE:
+      r->graph = true;
+      break;
+    case EK_INPUT:
+      r->input = true;
+      r->props.push_back(n.prop);
+      break;
+    case EK_VAR:
+      r->vars.insert(n.alias);
+      r->props.push_back(n.prop);
+      break;
+    default: break;
+  }
+  for (auto& k : n.kids)
+    if (k) yr_refs(*k, r);
+}
+
+}  // namespace
+
+int32_t nbg_yield(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq, nbg_rows** out) {
+  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  // ---- 1. arguments
+  if (rq->num_yields < 1) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: no YIELD column");
+  if (!rq->input_names || !rq->yield_exprs || !rq->yield_lens) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: null argument");
+  if (int32_t rc = guard_rows(E, "YIELD", {in})) return rc;
+  const int nc = in->ncols;
+  std::vector<std::string> names;
+  if (int32_t rc = copy_input_names(E, "YIELD", rq->input_names, nc, &names)) return rc;
+  std::string err;
+  std::unique_ptr<Node> where;
+  if (rq->where && rq->where_len) {
+    where = decode_expr(rq->where, rq->where_len, &err);
+    if (!where) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: WHERE: " + err);
+  }
+  std::vector<std::unique_ptr<Node>> given;
+  for (int y = 0; y < rq->num_yields; ++y) {
+    if (!rq->yield_exprs[y] || !rq->yield_lens[y]) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: an empty expression");
+    given.push_back(decode_expr(rq->yield_exprs[y], rq->yield_lens[y], &err));
+    if (!given.back()) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: " + err);
+    if (rq->yield_funs && (rq->yield_funs[y] < NBG_AGG_NONE || rq->yield_funs[y] > NBG_AGG_BIT_XOR))
+      return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: unknown function");
+  }
+  // ---- 2.
+  if (int32_t rc = guard_partitioned(E, "YIELD")) return rc;
+  // ---- `$-.*' / `$var.*' (YieldClauseWrapper::prepare): every input column, in order
+  std::vector<std::unique_ptr<Node>> yields;
+  std::vector<int32_t> funs;
+  YrRefs refs;
+  if (where) yr_refs(*where, &refs);
+  for (int y = 0; y < rq->num_yields; ++y) {
+    Node& n = *given[y];
+    const int32_t f = rq->yield_funs ? rq->yield_funs[y] : NBG_AGG_NONE;
+    if ((n.kind == EK_INPUT || n.kind == EK_VAR) && n.prop == "*") {
+      if (n.kind == EK_INPUT) refs.input = true;
+      else refs.vars.insert(n.alias);
+      for (int c = 0; c < nc; ++c) {
+        auto col = std::make_unique<Node>();
+        col->kind = n.kind;
+        col->alias = n.alias;
+        col->prop = names[c];
+        yields.push_back(std::move(col));
+        funs.push_back(f);
+      }
+      continue;
+    }
+    yr_refs(n, &refs);
+    yields.push_back(std::move(given[y]));
+    funs.push_back(f);
+  }
+  const int ny = (int)yields.size();
+  // ---- 3. checkAggFun (:33-58), syntaxCheck (:116-122)
+  bool agg = false;
+  for (int32_t f : funs) agg = agg || f != NBG_AGG_NONE;
+  if (agg)
+    for (int y = 0; y < ny; ++y)
+      if ((yields[y]->kind == EK_INPUT || yields[y]->kind == EK_VAR) && funs[y] == NBG_AGG_NONE)
+        return E.fail(NBG_E_SYNTAX_ERROR,
+                      "Input columns without aggregation are not supported in YIELD statement without GROUP BY, near `" +
+                          yields[y]->prop + "'");
+  if (refs.graph) return E.fail(NBG_E_SYNTAX_ERROR, "Only support input and variable in yield sentence.");
+  // ---- 4. (:124-135)
+  if (refs.input && !refs.vars.empty()) return E.fail(NBG_E_EXECUTION_ERROR, "Not support both input and variable.");
+  if (refs.vars.size() > 1) return E.fail(NBG_E_EXECUTION_ERROR, "Only one variable allowed to use.");
+  // ---- 5. no rows: one column per YIELD
+  if (!in->count) {
+    *out = new_rows(E, std::min(ny, (int)MAX_YIELDS));
+    return NBG_OK;
+  }
+  // ---- 6. getOutputSchema (:298-316): getFieldIndex, the first column of that name
+  auto find_col = [&](const std::string& n) {
+    auto it = std::find(names.begin(), names.end(), n);
+    return it == names.end() ? -1 : (int)(it - names.begin());
+  };
+  for (const std::string& p : refs.props)
+    if (find_col(p) < 0)
+      return E.fail(NBG_E_EXECUTION_ERROR,
+                    "column `" + p + "' not exist in " + (refs.vars.empty() ? "input." : "variable."));
+  // ---- 7. device scope
+  if (agg) return E.fail(NBG_E_UNSUPPORTED, "YIELD: aggregate functions without GROUP BY");
+  if (in->misaligned || in->float_col)
+    return E.fail(NBG_E_UNSUPPORTED, "YIELD: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (ny > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "YIELD: more than NBG_MAX_YIELDS columns");
+  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: the rows have no columns");
+  if (in->count > 0xFFFFFFFFull) return E.fail(NBG_E_UNSUPPORTED, "YIELD: an input of 2^32 rows or more");
+  const InputCols cols(in);
+  const std::vector<VKind>& kinds = cols.kind;
+  // a use: `bare' is a YIELD column that is exactly the input column
+  auto check_use = [&](int c, bool bare) -> int32_t {
+    if (cols.mixed[c]) return E.fail(NBG_E_UNSUPPORTED, "YIELD: column `" + names[c] + "' mixes value kinds");
+    if (kinds[c] != VK_STRING) return NBG_OK;
+    if (!bare && cols.outside[c])
+      return E.fail(NBG_E_UNSUPPORTED, "YIELD: column `" + names[c] + "' can hold strings outside the dictionary");
+    if (bare && cols.respelt[c])
+      return E.fail(NBG_E_UNSUPPORTED, "YIELD: column `" + names[c] + "' spells different constants per OVER type");
+    return NBG_OK;
+  };
+  {
+    YrRefs wr;
+    if (where) yr_refs(*where, &wr);
+    for (const std::string& p : wr.props)
+      if (int32_t rc = check_use(find_col(p), false)) return rc;
+    for (int y = 0; y < ny; ++y) {
+      const bool bare = yields[y]->kind == EK_INPUT || yields[y]->kind == EK_VAR;
+      YrRefs yr;
+      yr_refs(*yields[y], &yr);
+      for (const std::string& p : yr.props)
+        if (int32_t rc = check_use(find_col(p), bare)) return rc;
+    }
+  }
+  // ---- compile: WHERE first, then the YIELDs, one program for every row
+  CompileEnv cenv = stage_env(E, true);
+  cenv.input_names = &names;
+  cenv.input_kinds = &kinds;
+  ProgramBuilder pb;
+  YrPlan plan;
+  plan.ncols = ny;
+  bool where_false = false;
+  if (where) {
+    Compiled c;
+    if (int32_t rc = compile_expr(*where, cenv, pb, &c, &err)) return E.fail(rc, "YIELD: " + err);
+    if (c.is_const) {
+      bool tv;
+      switch (c.kind) {   // Expression::asBool
+        case VK_STRING: tv = c.const_str.empty(); break;
+        case VK_DOUBLE: { double d; memcpy(&d, &c.const_bits, 8); tv = d != 0.0; break; }
+        default: tv = c.const_bits != 0;
+      }
+      where_false = !tv;
+      pb.code.clear();
+    } else {
+      const int r = c.reg;
+      if (c.kind == VK_INT) pb.code.push_back(Ins{OP_TRUTHY_I, (uint8_t)r, (uint8_t)r, 0, 0, 0});
+      else if (c.kind == VK_DOUBLE) pb.code.push_back(Ins{OP_TRUTHY_F, (uint8_t)r, (uint8_t)r, 0, 0, 0});
+      else if (c.kind == VK_STRING)
+        pb.code.push_back(Ins{OP_TRUTHY_S, (uint8_t)r, (uint8_t)r, 0, 0, string_code(E.snap.strings, "")});
+      plan.where_len = (int)pb.code.size();
+      plan.where_reg = r;
+    }
+    pb.next_reg = 0;   // WHERE registers are dead once its value is read
+  }
+  std::unique_ptr<nbg_rows> res(new_rows(E, ny));
+  res->derived = in->derived;
+  ColTypeEnv tenv;
+  tenv.input_names = &names;
+  tenv.input_kinds = &kinds;
+  std::set<int32_t> direct;   // input columns passed through without the interpreter
+  for (int y = 0; y < ny; ++y) {
+    if (yields[y]->kind == EK_INPUT || yields[y]->kind == EK_VAR) {   // a bare column: copied as it is
+      const int col = find_col(yields[y]->prop);
+      plan.yield_reg[y] = -2 - col;
+      direct.insert(col);
+      res->kinds[0][y] = kinds[col];
+      res->col_types[y] = natural_type_of(kinds[col]);
+      if (kinds[col] == VK_STRING) res->const_str[0][y] = cols.spell[col];
+      continue;
+    }
+    if (int32_t rc = compile_yield_column(E, "YIELD", *yields[y], cenv, tenv, pb, y, &plan, res.get())) return rc;
+  }
+  if (int32_t rc = finish_program(E, "YIELD", pb, &plan)) return rc;
+  if (where_false) {   // a constant-false WHERE: no row, no launch
+    *out = res.release();
+    return NBG_OK;
+  }
+  {
+    std::set<int32_t> wc, yc = direct;
+    for (int pc = 0; pc < (int)plan.code.size(); ++pc)
+      if (plan.code[pc].op == OP_COL) (pc < plan.where_len ? wc : yc).insert(plan.code[pc].aux);
+    plan.where_cols = (int)wc.size();
+    plan.yield_cols = (int)yc.size();
+  }
+  // ---- 8. the passes
+  DeviceInput d;
+  if (int32_t rc = device_input(E, "YIELD", in, &d)) return rc;
+  plan.str = E.dev_strings();
+  plan.now_sec = (int64_t)time(nullptr);
+  plan.rand_seed = query_rand_seed();
+  Workspace* ow = nullptr;
+  uint64_t n = 0;
+  if (int32_t rc = ws_yield_rows(d.w, E.stream, d.segs, plan, &ow, &n, &E.yr_prof, &err)) return E.fail(rc, err);
+  if (ow) adopt_rows(res.get(), ow, n, ny);
+  *out = res.release();
+  return NBG_OK;
+}
+
+// ============================================================================= FETCH PROP ON <tag>
+// FetchVerticesExecutor / FetchExecutor (src/graph/FetchVerticesExecutor.cpp:19-311,
+// src/graph/FetchExecutor.cpp:14-131) over a device-resident result; the kernels are in
+// fetchrows.hip and, beside the interpreter, kernels.hip.
+namespace {
+
+// what a YIELD tree of a FETCH references (ExpressionContext's has*Prop and aliasProps())
+struct FvRefs {
+  bool graph = false;   // $^ / $$
+  bool input = false;   // $- / $var
+  std::vector<std::pair<std::string, std::string>> alias;   // (alias, prop), in evaluation order
+};
+void fv_refs(const Node& n, FvRefs* r) {
+  switch (n.kind) {
+    case EK_SRCPROP: case EK_DSTPROP: r->graph = true; break;
+    case EK_INPUT: case EK_VAR: r->input = true; break;
+    case EK_ALIAS: case EK_RANK: case EK_DST: case EK_SRCID: case EK_TYPE: r->alias.emplace_back(n.alias, n.prop); break;
+    default: break;
+  }
+  for (auto& k : n.kids)
+    if (k) fv_refs(*k, r);
+}
+
+}  // namespace
+
+int32_t nbg_fetch_vertices(nbg_engine* h, const nbg_rows* in, const nbg_fetch_request* rq, nbg_rows** out) {
+  if (!h || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  // ---- 1. arguments
+  if (rq->num_yields < 0 || (rq->num_yields > 0 && (!rq->yield_exprs || !rq->yield_lens)))
+    return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null argument");
+  if (in) {
+    if (!rq->input_names || !rq->vid_col) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null argument");
+    if (int32_t rc = guard_rows(E, "FETCH", {in})) return rc;
+  } else if (!rq->vids && rq->num_vids) {
+    return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null vid list");
+  }
+  if (!E.finalized) return E.fail(NBG_E_STATE, "engine not finalized");
+  const int nc = in ? in->ncols : 1;
+  std::vector<std::string> names;
+  if (!in) names.emplace_back("id");
+  else if (int32_t rc = copy_input_names(E, "FETCH", rq->input_names, nc, &names)) return rc;
+  const std::string vid_col = in ? rq->vid_col : "id";
+  std::string err;
+  std::vector<std::unique_ptr<Node>> yields;
+  for (int y = 0; y < rq->num_yields; ++y) {
+    if (!rq->yield_exprs[y] || !rq->yield_lens[y]) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: an empty expression");
+    yields.push_back(decode_expr(rq->yield_exprs[y], rq->yield_lens[y], &err));
+    if (!yields.back()) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: " + err);
+  }
+  // ---- 2.
+  if (int32_t rc = guard_partitioned(E, "FETCH")) return rc;
+  // ---- 3. prepareClauses (:39-50), prepareVids (:79-81)
+  auto tit = E.tags.find(rq->tag_id);
+  const Schema* tsc = tit == E.tags.end() ? nullptr : tit->second.latest();
+  if (!tsc) return E.fail(NBG_E_EXECUTION_ERROR, "tag " + std::to_string(rq->tag_id) + " schema not exist.");
+  const std::string& tag_name = tit->second.name;
+  if (in && vid_col == "*") return E.fail(NBG_E_EXECUTION_ERROR, "Cant not use `*' to reference a vertex id column.");
+  // ---- no YIELD clause: every column of the latest schema, in order (FetchExecutor::setupColumns, :73-90)
+  if (!rq->num_yields)
+    for (const Column& col : tsc->cols) {
+      auto n = std::make_unique<Node>();
+      n->kind = EK_ALIAS;
+      n->alias = tag_name;
+      n->prop = col.name;
+      yields.push_back(std::move(n));
+    }
+  const int ny = (int)yields.size();
+  // ---- 4. prepareYield (FetchExecutor.cpp:50-68), before setupVids: diagnosed for an empty input too
+  FvRefs refs;
+  for (auto& y : yields) fv_refs(*y, &refs);
+  if (refs.graph) return E.fail(NBG_E_SYNTAX_ERROR, "tag.prop and edgetype.prop are supported in fetch sentence.");
+  if (refs.input) return E.fail(NBG_E_SYNTAX_ERROR, "`$-' and `$variable' not supported in fetch yet.");
+  for (auto& ap : refs.alias)
+    if (ap.first != tag_name)
+      return E.fail(NBG_E_SYNTAX_ERROR,
+                    "Near [" + ap.first + "." + ap.second + "], tag or edge should be declared in statement first.");
+  // ---- 5. no rows (onEmptyInputs, FetchExecutor.cpp:99-107): one column per YIELD
+  const uint64_t nin = in ? in->count : rq->num_vids;
+  if (!nin) {
+    *out = new_rows(E, std::min(ny, (int)MAX_YIELDS));
+    return NBG_OK;
+  }
+  // ---- 6. getVIDs -> RowReader::getVid (InterimResult.cpp:29-72, RowReader.cpp:569-576): INT and VID
+  // columns only; getPropNames (:142-153, :110-115); the storage request names a prop the schema lacks
+  int vcol = 0;
+  bool vid_mixed = false;
+  if (in) {
+    auto it = std::find(names.begin(), names.end(), vid_col);
+    vcol = it == names.end() ? -1 : (int)(it - names.begin());
+    const InputCols cols(in);
+    vid_mixed = vcol >= 0 && cols.mixed[vcol];
+    if (vcol < 0 || cols.kind[vcol] != VK_INT || (cols.type[vcol] != NBG_T_INT && cols.type[vcol] != NBG_T_VID))
+      return E.fail(NBG_E_EXECUTION_ERROR, "Column `" + vid_col + "' not found");
+  }
+  if (refs.alias.empty()) return E.fail(NBG_E_EXECUTION_ERROR, "No props declared.");
+  for (auto& ap : refs.alias)
+    if (tsc->find(ap.second) < 0) return E.fail(NBG_E_EXECUTION_ERROR, "Get props failed");
+  // ---- 7. device scope
+  if (in && (in->misaligned || in->float_col))
+    return E.fail(NBG_E_UNSUPPORTED, "FETCH: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (vid_mixed) return E.fail(NBG_E_UNSUPPORTED, "FETCH: column `" + vid_col + "' mixes value kinds");
+  if (ny > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "FETCH: more than NBG_MAX_YIELDS columns");
+  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: the rows have no columns");
+  if (nin > 0xFFFFFFFFull) return E.fail(NBG_E_UNSUPPORTED, "FETCH: an input of 2^32 rows or more");
+  auto dit = E.snap.tags.find(rq->tag_id);
+  if (dit == E.snap.tags.end() || !dit->second.decoded || !E.snap.d_tcols || !E.snap.d_tpres || !E.snap.d_vids)
+    return E.fail(NBG_E_UNSUPPORTED, "FETCH: tag tables missing");
+  const DevTag& dtag = dit->second;
+  // ---- compile: the YIELDs, one program for every found row
+  CompileEnv cenv = stage_env(E, true);
+  cenv.dtags = &E.snap.tags;
+  cenv.fetch_tag = &tag_name;
+  ProgramBuilder pb;
+  FvPlan plan;
+  plan.y.ncols = ny;
+  plan.vid_col = vcol;
+  plan.pres = dtag.decoded;
+  std::unique_ptr<nbg_rows> res(new_rows(E, ny));
+  ColTypeEnv tenv;
+  std::set<int32_t> tcols_read;
+  for (int y = 0; y < ny; ++y) {
+    const Node& n = *yields[y];
+    if (n.kind == EK_ALIAS) {   // a bare `tag.prop': the found vertex's column as it is
+      const int col = tsc->find(n.prop);
+      if (col >= (int)dtag.kind.size()) return E.fail(NBG_E_UNSUPPORTED, "FETCH: tag tables missing");
+      plan.y.yield_reg[y] = -2 - (dtag.col_base + col);
+      tcols_read.insert(dtag.col_base + col);
+      res->kinds[0][y] = dtag.kind[col];
+      res->col_types[y] = tsc->cols[col].type;   // FetchExecutor::prepareYield, :37-42
+      if (res->col_types[y] == NBG_T_FLOAT) return E.fail(NBG_E_UNSUPPORTED, "FETCH: a bare FLOAT prop (a FLOAT result column)");
+      continue;
+    }
+    if (int32_t rc = compile_yield_column(E, "FETCH", n, cenv, tenv, pb, y, &plan.y, res.get())) return rc;   // :43-47
+  }
+  if (int32_t rc = finish_program(E, "FETCH", pb, &plan.y)) return rc;
+  for (const Ins& i : plan.y.code)
+    if (i.op == OP_TAGS_E) tcols_read.insert(i.aux & 0xFFFF);
+  plan.tag_cols = (int)tcols_read.size();
+  // ---- 8. the passes
+  DeviceInput d;
+  if (in) {
+    if (int32_t rc = device_input(E, "FETCH", in, &d)) return rc;
+  } else {   // the literal vids: ws_fetch_vertices uploads them into a temporary one-column result
+    if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+    d.segs.emplace_back(0, nin);
+  }
+  plan.y.str = E.dev_strings();
+  plan.y.now_sec = (int64_t)time(nullptr);
+  plan.y.rand_seed = query_rand_seed();
+  plan.vids = E.snap.d_vids;
+  plan.nv = E.snap.nv;
+  plan.visible = E.snap.d_visible;
+  plan.tcols = E.snap.d_tcols;
+  plan.tpres = E.snap.d_tpres;
+  // (a knob of tools/fetch_probe.py alone, like NBG_SP_*: not part of the interface.  Read per call,
+  // so the probe can A/B both searches in one process; a getenv beside milliseconds of kernels)
+  if (const char* s = getenv("NBG_FETCH_SEARCH")) plan.search = !strcmp(s, "two-level") ? 2 : 0;
+  Workspace* ow = nullptr;
+  uint64_t n = 0;
+  if (int32_t rc = ws_fetch_vertices(d.w, in ? nullptr : rq->vids, E.stream, d.segs, plan, &ow, &n, &E.fv_prof, &err)) return E.fail(rc, err);
+  // ---- YIELD DISTINCT (processResult's uniqResult, :159, :221-228): one row per distinct output
+  // row, through nbg_set_op's row table: the UNION DISTINCT of the result's two halves
+  if (ow && rq->distinct && n > 1) {
+    RowsWs first;   // the result before DISTINCT
+    first.w = ow;
+    SoPlan sp;
+    sp.op = NBG_SET_UNION;
+    sp.distinct = 1;
+    sp.ncols = ny;
+    for (int c = 0; c < ny; ++c) sp.dbl[c] = res->kinds[0][c] == VK_DOUBLE;   // (-0.0 == 0.0, as nbg_set_op)
+    const uint64_t half = n / 2;
+    ow = nullptr;
+    if (int32_t rc = ws_set_op(first.w, first.w, E.stream, {{0, half}}, {{half, n - half}}, sp, &ow, &n, &E.so_prof, &err))
+      return E.fail(rc, err);
+  }
+  if (ow) adopt_rows(res.get(), ow, n, ny);
+  *out = res.release();
+  return NBG_OK;
+}
+
+}  // extern "C"

@@ -53,20 +53,10 @@ hipError_t launch_yr_scan(const uint32_t* count, uint32_t n, uint32_t* base, YrS
 }
 
 int32_t ws_yield_rows(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
-                      const YrPlan& plan, Workspace** outw, uint64_t* rows, YrProf* prof, std::string* err) {
+                      const YrPlan& plan, Workspace** outw, uint64_t* rows, StageProf<YR_KINDS>* prof, std::string* err) {
   *outw = nullptr;
   *rows = 0;
-  hipError_t he = hipSuccess;
-  const char* what = "";
-  auto failed = [&](hipError_t e, const char* w) {
-    he = e;
-    what = w;
-    return e != hipSuccess;
-  };
-  auto code = [&]() -> int32_t {
-    if (err) *err = std::string("YIELD: ") + what + ": " + hipGetErrorString(he);
-    return he == hipErrorOutOfMemory ? NBG_E_OUT_OF_MEMORY : NBG_E_DEVICE;
-  };
+  StageStatus cs("YIELD");
   uint64_t n = 0;
   for (auto& sg : segs) n += sg.second;
   if (plan.ncols < 1 || plan.ncols > MAX_YIELDS || !n || n > 0xFFFFFFFFull || plan.code.size() + plan.data.size() > (size_t)MAX_PROGRAM ||
@@ -76,80 +66,35 @@ int32_t ws_yield_rows(Workspace* inw, hipStream_t stream, const std::vector<std:
     return NBG_E_INVALID_ARGUMENT;
   }
 
-  // the result: a workspace holding nothing but its rows (what the row accessors read)
-  struct WsGuard {
-    Workspace* w = nullptr;
-    ~WsGuard() { if (w) ws_destroy(w); }
-  } res;
-  auto new_result = [&](uint64_t nout) {
-    res.w = new Workspace();
-    res.w->stream = stream;
-    hipError_t e = hipMalloc((void**)&res.w->d_row_cols, MAX_YIELDS * sizeof(int64_t*));
-    if (e == hipSuccess) e = ws_reserve_rows(res.w, nout, plan.ncols);
-    if (e != hipSuccess) (void)hipGetLastError();
-    return e;
-  };
-
+  RowsWs res;
   StageScratch sc;   // (declared before the timer: the timer's events are resolved first)
-  StageTimer<YrProf> tm{prof, stream, {}, nullptr};
-  const std::vector<uint64_t> chunks = stage_chunks(segs, 0, n);
-  const uint32_t nchunks = (uint32_t)(chunks.size() / 3);
-  const unsigned grid = std::min<unsigned>(std::max<uint32_t>(nchunks, 1), STAGE_GRID);
-  std::vector<Ins> image(plan.code);
-  image.insert(image.end(), plan.data.begin(), plan.data.end());
-  uint64_t* d_chunks = nullptr;
-  Ins* d_prog = nullptr;
-  YrState* st = nullptr;
-  // (a pageable source is staged by the runtime before the call returns)
-  if (failed(sc.alloc((void**)&d_chunks, chunks.size() * 8), "chunk list") ||
-      failed(sc.alloc((void**)&d_prog, image.size() * sizeof(Ins)), "program") ||
-      failed(sc.alloc((void**)&st, sizeof(YrState)), "state") ||
-      failed(hipMemcpyAsync(d_chunks, chunks.data(), chunks.size() * 8, hipMemcpyHostToDevice, stream), "chunk upload") ||
-      (!image.empty() &&
-       failed(hipMemcpyAsync(d_prog, image.data(), image.size() * sizeof(Ins), hipMemcpyHostToDevice, stream), "program upload")) ||
-      failed(hipMemsetAsync(st, 0, sizeof(YrState), stream), "state clear") ||
-      failed(hipStreamSynchronize(stream), "uploads"))
-    return code();
-
+  StageTimer<YR_KINDS> tm{prof, stream, {}, nullptr};
+  StageChunks ch;
   YrArgs a{};
-  a.chunk = d_chunks;
-  a.nchunks = nchunks;
-  a.cols = (const int64_t* const*)inw->d_row_cols;
-  a.prog = d_prog;
-  a.code_len = (int)plan.code.size();
-  a.where_len = plan.where_len;
-  a.where_reg = plan.where_reg;
-  a.err = &st->err;
-  a.ncols = plan.ncols;
-  for (int c = 0; c < plan.ncols; ++c) {
-    a.yield_reg[c] = plan.yield_reg[c];
-    a.yield_const[c] = plan.yield_const[c];
-  }
-  a.str = plan.str;
-  a.now_sec = plan.now_sec;
-  a.rand_seed = plan.rand_seed;
+  YrState* st = nullptr;
+  if (ch.upload(cs, sc, stream, segs, 0, n) || yr_setup(cs, sc, stream, plan, ch, inw, &a, &st)) return cs.code(err);
 
   uint64_t nout = n;
   YrState got{};
   if (plan.where_reg >= 0) {
     uint32_t* ccount = nullptr;
     uint32_t* cbase = nullptr;
-    if (failed(sc.alloc((void**)&a.keep, n), "keep flags") || failed(sc.alloc((void**)&ccount, (size_t)nchunks * 4), "chunk counts") ||
-        failed(sc.alloc((void**)&cbase, (size_t)nchunks * 4), "chunk bases"))
-      return code();
+    if (cs.failed(sc.alloc((void**)&a.keep, n), "keep flags") || cs.failed(sc.alloc((void**)&ccount, (size_t)ch.n * 4), "chunk counts") ||
+        cs.failed(sc.alloc((void**)&cbase, (size_t)ch.n * 4), "chunk bases"))
+      return cs.code(err);
     a.ccount = ccount;
     a.cbase = cbase;
     tm.begin();
-    he = launch_yr_filter(a, plan.nregs, grid, stream);
+    hipError_t he = launch_yr_filter(a, plan.nregs, ch.grid, stream);
     tm.end(YR_K_FILTER, (double)n * (8.0 * plan.where_cols + 1.0));
-    if (failed(he, "k_yr_filter")) return code();
+    if (cs.failed(he, "k_yr_filter")) return cs.code(err);
     tm.begin();
-    hipLaunchKernelGGL(k_yr_scan, dim3(1), dim3(BLOCK), 0, stream, ccount, nchunks, cbase, st);
-    tm.end(YR_K_SCAN, (double)nchunks * 8.0);
-    if (failed(hipGetLastError(), "k_yr_scan") ||
-        failed(hipMemcpyAsync(&got, st, sizeof(YrState), hipMemcpyDeviceToHost, stream), "kept rows read") ||
-        failed(hipStreamSynchronize(stream), "filter"))
-      return code();
+    he = launch_yr_scan(ccount, ch.n, cbase, st, stream);
+    tm.end(YR_K_SCAN, (double)ch.n * 8.0);
+    if (cs.failed(he, "k_yr_scan") ||
+        cs.failed(hipMemcpyAsync(&got, st, sizeof(YrState), hipMemcpyDeviceToHost, stream), "kept rows read") ||
+        cs.failed(hipStreamSynchronize(stream), "filter"))
+      return cs.code(err);
     if (got.err) {
       if (err) *err = "YIELD: an evaluation error in the WHERE clause";
       return NBG_E_EXECUTION_ERROR;
@@ -162,21 +107,20 @@ int32_t ws_yield_rows(Workspace* inw, hipStream_t stream, const std::vector<std:
     if (!nout) return NBG_OK;
   }
 
-  if (failed(new_result(nout), "result rows")) return code();
+  if (cs.failed(res.reserve(stream, nout, plan.ncols), "result rows")) return cs.code(err);
   for (int c = 0; c < plan.ncols; ++c) a.out[c] = ws_row_col(res.w, c);
   a.cap = nout;
   tm.begin();
-  he = launch_yr_emit(a, plan.nregs, grid, stream);
+  const hipError_t he = launch_yr_emit(a, plan.nregs, ch.grid, stream);
   tm.end(YR_K_EMIT, (double)n * (a.keep ? 1.0 : 0.0) + (double)nout * 8.0 * (plan.yield_cols + plan.ncols));
-  if (failed(he, "k_yr_emit") || failed(hipMemcpyAsync(&got, st, sizeof(YrState), hipMemcpyDeviceToHost, stream), "error word read") ||
-      failed(hipStreamSynchronize(stream), "emission"))
-    return code();
+  if (cs.failed(he, "k_yr_emit") || cs.failed(hipMemcpyAsync(&got, st, sizeof(YrState), hipMemcpyDeviceToHost, stream), "error word read") ||
+      cs.failed(hipStreamSynchronize(stream), "emission"))
+    return cs.code(err);
   if (got.err) {
     if (err) *err = "YIELD: an evaluation error in a YIELD column";
     return NBG_E_EXECUTION_ERROR;
   }
-  *outw = res.w;
-  res.w = nullptr;
+  *outw = res.release();
   *rows = nout;
   return NBG_OK;
 }

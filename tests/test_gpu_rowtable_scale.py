@@ -8,7 +8,7 @@ never from the device.  Every structural condition is asserted from the result's
 
 The big table.  A GO's final step runs at most EXPAND_GRID = 2048 workgroups per OVER type and each
 appends to one segment, so a GO result over one edge type has at most 2048 segments.  More than
-OB_GRID = 2048 chunks (ob_chunks cuts every segment into pieces of OB_CHUNK = 2048 rows) therefore
+OB_GRID = 2048 chunks (stage_chunks cuts every segment into pieces of OB_CHUNK = 2048 rows) therefore
 needs segments longer than a chunk: a little over 2048 * 2048 rows, whatever the GO's shape.  The
 fixture loads more sources than that needs and bisects, over trial GOs' segment lists, the smallest
 number of sources whose result has more than OB_GRID chunks and a segment longer than OB_CHUNK
@@ -146,7 +146,7 @@ BIG_AGGS = [("COUNT", None), ("SUM", "i"), ("MAX", "i"), ("MIN", "i"), ("MAX", "
 @pytest.mark.parametrize("keys", [["g"], ["b"], []], ids=["g_global", "b_lds", "const"])
 def test_big_group_by(big, keys):
     ref = rt.group_ref(big.t, keys, BIG_AGGS, big.idx)
-    nacc = 9                        # COUNT, and one accumulator per aggregate after it (engine.cpp's plan)
+    nacc = 9                        # COUNT, and one accumulator per aggregate after it (stages.cpp's plan)
     if keys == ["g"]:
         assert ref.n > 65536 and nacc * ref.n * 8 > GB_LDS_BYTES
     if keys == ["b"]:
@@ -159,7 +159,7 @@ def test_big_group_by(big, keys):
 
 # ------------------------------------------------------------------------------ 3 - 5. the small table
 AGGS = [("COUNT", None), ("SUM", "v"), ("MIN", "v"), ("BIT_XOR", "v"), ("SUM", "y"), ("MAX", "v"), ("MIN", "y"), ("MAX", "y")]
-# the plan of nbg_group_by (engine.cpp): slot 0 is COUNT, which COUNT(*) reads; every other
+# the plan of nbg_group_by (stages.cpp): slot 0 is COUNT, which COUNT(*) reads; every other
 # aggregate here takes one slot of its own (SUM, MIN, BIT_XOR, SUM, MAX, MIN, MAX): nacc = 1 + 7 = 8.
 NACC = 8
 G_LDS = GB_LDS_BYTES // (NACC * 8)          # 256 groups: 8 * 256 * 8 == GB_LDS_BYTES, the last LDS case
