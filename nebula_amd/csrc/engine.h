@@ -89,6 +89,9 @@ struct Engine {
   std::unique_ptr<Comm> comm;
   uint64_t npad = 0;
   bool partitioned() const { return cfg.num_gpus > 1; }
+  // max_edge_returned_per_vertex: the edges one vertex contributes per type (nbg_create turns a
+  // non-positive setting into INT32_MAX, so the field is always positive)
+  uint32_t edge_cap() const { return (uint32_t)cfg.max_edge_returned_per_vertex; }
   // partitioned: every rank's dictionary (global id order) and every vertex's out-degree per positive
   // type over the global id space, host copies from finalize, so that every rank bounds a GO first
   // hop's edges per owner alike (go_launch sends a small hop as slot arrays instead of bitmaps)
@@ -183,6 +186,13 @@ void path_slots_release(Engine& E); // completes outstanding path tickets, frees
 // Make *wsp free for a new query: if live device rows still sit in it, the rows take the
 // workspace over and *wsp becomes a fresh one on `stream` (profiling state carried over).
 int32_t ws_release(Engine& E, Workspace** wsp, hipStream_t stream);
+// A fresh query workspace on `stream`: created, given its partition buffers (on `comm`) and the
+// prepared statements' row reserve, with the profiling state of `old` (may be null).  nullptr and
+// *err on failure; nothing is held then.
+Workspace* ws_fresh(Engine& E, uint64_t max_frontier, uint64_t e_max, hipStream_t stream, Comm* comm, Workspace* old,
+                    std::string* err);
+int32_t materialize_rows(::nbg_rows* r);   // engine.cpp: a result's rows into host memory (nbg_rows_fetch)
+void go_drain(Engine& E);                  // go.cpp: completes and frees the tickets never waited for
 
 }  // namespace nbg
 

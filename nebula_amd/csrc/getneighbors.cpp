@@ -580,7 +580,7 @@ static int32_t get_neighbors(Engine& E, const nbg_gn_request* rq, nbg_gn_respons
 
   if (tr_.on) tr_.mark(3);
   // --- responses per requested vertex, in part order (QueryBaseProcessor::genBuckets order)
-  const uint64_t cap = (uint64_t)(E.cfg.max_edge_returned_per_vertex <= 0 ? 0x7fffffff : E.cfg.max_edge_returned_per_vertex);
+  const uint64_t cap = E.edge_cap();
   const auto& dict = E.snap.strings;
   static const std::string kEmpty;
   auto str_of = [&](int64_t code) -> const std::string& {

@@ -2617,6 +2617,21 @@ static bool bits_off() {
   return off;
 }
 
+// One k_expand launch of mode M: over the start list in the kernel arguments when `il` is given,
+// else over the device list.
+template <Mode M>
+static void launch_expand(dim3 grid, size_t lds, hipStream_t stream, const ExpandArgs& a, const unsigned long long* acc,
+                          const uint32_t* seg_end, const uint32_t* seg_rs, uint8_t* flags, const FinalParams& fp,
+                          const BfsParams& bp, unsigned long long* stat_e, unsigned long long* stat_n,
+                          const InlineList* il) {
+  if (il)
+    hipLaunchKernelGGL((k_expand<M, true>), grid, dim3(BLOCK), lds, stream, a, acc, seg_end, seg_rs, flags, fp, bp,
+                       stat_e, stat_n, *il);
+  else
+    hipLaunchKernelGGL(k_expand<M>, grid, dim3(BLOCK), lds, stream, a, acc, seg_end, seg_rs, flags, fp, bp, stat_e,
+                       stat_n, NoInline{});
+}
+
 hipError_t ws_expand_mark(Workspace* w, const ExpandArgs& a0, uint64_t n_bound, uint64_t e_bound, int step, int tix,
                           const InlineList* il, const ExpandArgs* next0) {
   if (step > MAX_STEPS || tix >= MAX_TYPES_Q) return hipErrorInvalidValue;
@@ -2652,19 +2667,14 @@ hipError_t ws_expand_mark(Workspace* w, const ExpandArgs& a0, uint64_t n_bound, 
     }
     w->hop_bits = true;
   }
+  const auto launch = a0.bt ? launch_expand<MARKB> : launch_expand<MARK>;
   if (inline_start_list(w, tix, il)) {   // no k_relist: the list travels in the kernel arguments
     ExpandArgs a = a0;
     a.frontier = nullptr;
     a.tsplit = nullptr;
     hipEvent_t p = prof_begin(w, K_EXPAND_MARK);
-    if (a.bt)
-      hipLaunchKernelGGL((k_expand<MARKB, true>), dim3(mark_grid(il->n, il->total)), dim3(BLOCK), 0, w->stream, a,
-                         (const unsigned long long*)nullptr, w->seg_end, w->seg_rs, w->flags, FinalParams{},
-                         bp, &w->q->e_st[step][tix], &w->q->step_n[step], *il);
-    else
-      hipLaunchKernelGGL((k_expand<MARK, true>), dim3(mark_grid(il->n, il->total)), dim3(BLOCK), 0, w->stream, a,
-                         (const unsigned long long*)nullptr, w->seg_end, w->seg_rs, w->flags, FinalParams{},
-                         bp, &w->q->e_st[step][tix], &w->q->step_n[step], *il);
+    launch(dim3(mark_grid(il->n, il->total)), 0, w->stream, a, nullptr, w->seg_end, w->seg_rs, w->flags, FinalParams{},
+           bp, &w->q->e_st[step][tix], &w->q->step_n[step], il);
     prof_end(w, p, K_EXPAND_MARK, step, tix);
     return hipGetLastError();
   }
@@ -2675,14 +2685,8 @@ hipError_t ws_expand_mark(Workspace* w, const ExpandArgs& a0, uint64_t n_bound, 
   FinalParams fp{};
   fp.err_flag = &w->q->err;   // (SPLIT_BAD)
   hipEvent_t p = prof_begin(w, K_EXPAND_MARK);
-  if (a.bt)
-    hipLaunchKernelGGL(k_expand<MARKB>, dim3(mark_grid(n_bound, e_bound)), dim3(BLOCK), 0, w->stream, a, L.acc,
-                       set_end(w, L.set), set_rs(w, L.set), w->flags, fp, bp, &w->q->e_st[step][tix], L.stat_n,
-                       NoInline{});
-  else
-    hipLaunchKernelGGL(k_expand<MARK>, dim3(mark_grid(n_bound, e_bound)), dim3(BLOCK), 0, w->stream, a, L.acc,
-                       set_end(w, L.set), set_rs(w, L.set), w->flags, fp, bp, &w->q->e_st[step][tix], L.stat_n,
-                       NoInline{});
+  launch(dim3(mark_grid(n_bound, e_bound)), 0, w->stream, a, L.acc, set_end(w, L.set), set_rs(w, L.set), w->flags, fp,
+         bp, &w->q->e_st[step][tix], L.stat_n, nullptr);
   prof_end(w, p, K_EXPAND_MARK, step, tix);
   return hipGetLastError();
 }
@@ -2917,20 +2921,11 @@ hipError_t ws_expand_final(Workspace* w, const ExpandArgs& a0, uint64_t n_bound,
   hipEvent_t p = prof_begin(w, K_EXPAND_FINAL);
   const dim3 grid(final_grid(n_bound, e_bound));
   unsigned long long* e_st = &w->q->e_st[step][tix];
-  if (inl) {
-    if (dst_only)
-      hipLaunchKernelGGL((k_expand<FINALD, true>), grid, dim3(BLOCK), 0, w->stream, a, L.acc, l_end, l_rs,
-                         w->flags, fp, BfsParams{}, e_st, L.stat_n, *il);
-    else if (wide)
-      hipLaunchKernelGGL((k_expand<FINALY, true>), grid, dim3(BLOCK), 0, w->stream, a, L.acc, l_end, l_rs,
-                         w->flags, fp, BfsParams{}, e_st, L.stat_n, *il);
-    else if (fp.fast.enabled)
-      hipLaunchKernelGGL((k_expand<FINALF, true>), grid, dim3(BLOCK), 0, w->stream, a, L.acc, l_end, l_rs,
-                         w->flags, fp, BfsParams{}, e_st, L.stat_n, *il);
-    else
-      hipLaunchKernelGGL((k_expand<FINAL, true>), grid, dim3(BLOCK), lds, w->stream, a, L.acc, l_end, l_rs,
-                         w->flags, fp, BfsParams{}, e_st, L.stat_n, *il);
-  } else if (dst_only && lean_final() && fp.fast.dst_yield && a.dst_vid && (!fp.fast.has_where || fp.fast.wcol)) {
+  // (lds is 0 for the three fast modes)
+  const auto launch = dst_only ? launch_expand<FINALD>
+                      : wide ? launch_expand<FINALY>
+                      : fp.fast.enabled ? launch_expand<FINALF> : launch_expand<FINAL>;
+  if (!inl && dst_only && lean_final() && fp.fast.dst_yield && a.dst_vid && (!fp.fast.has_where || fp.fast.wcol)) {
     FinalDstArgs fa{};
     fa.acc = L.acc;
     fa.seg_end = l_end;
@@ -2967,18 +2962,8 @@ hipError_t ws_expand_final(Workspace* w, const ExpandArgs& a0, uint64_t n_bound,
       prof_end(w, p, K_EXPAND_FINAL, step, tix, 0.0, 0.0);   // (the profile's open event closed)
       return le;
     }
-  } else if (dst_only) {
-    hipLaunchKernelGGL(k_expand<FINALD>, grid, dim3(BLOCK), 0, w->stream, a, L.acc, l_end, l_rs, w->flags,
-                       fp, BfsParams{}, e_st, L.stat_n, NoInline{});
-  } else if (wide) {
-    hipLaunchKernelGGL(k_expand<FINALY>, grid, dim3(BLOCK), 0, w->stream, a, L.acc, l_end, l_rs, w->flags,
-                       fp, BfsParams{}, e_st, L.stat_n, NoInline{});
-  } else if (fp.fast.enabled) {
-    hipLaunchKernelGGL(k_expand<FINALF>, grid, dim3(BLOCK), 0, w->stream, a, L.acc, l_end, l_rs, w->flags,
-                       fp, BfsParams{}, e_st, L.stat_n, NoInline{});
   } else {
-    hipLaunchKernelGGL(k_expand<FINAL>, grid, dim3(BLOCK), lds, w->stream, a, L.acc, l_end, l_rs, w->flags,
-                       fp, BfsParams{}, e_st, L.stat_n, NoInline{});
+    launch(grid, lds, w->stream, a, L.acc, l_end, l_rs, w->flags, fp, BfsParams{}, e_st, L.stat_n, inl ? il : nullptr);
   }
   prof_end(w, p, K_EXPAND_FINAL, step, tix, full_row_ptr ? -1.0 : (double)edge_columns_read(prog), (double)fp.nyields);
   w->final_grid[tix] = final_grid(n_bound, e_bound);
@@ -3517,7 +3502,7 @@ hipError_t ws_set_partition(Workspace* w, Comm* comm, uint64_t npad) {
 }
 
 // A rank whose preparation of a query failed still takes part in the query's collectives (the
-// fast path of a partitioned GO, engine.cpp go_launch): `hops` all-to-alls of the zero bitmap
+// fast path of a partitioned GO, go.cpp go_agree): `hops` all-to-alls of the zero bitmap
 // `send0` (G segments of seg_bytes; received into `recv`, never read), then the statistics
 // all-reduce with zero statistics and its status word.  Synchronous; *agreed = the first failing
 // rank's status.

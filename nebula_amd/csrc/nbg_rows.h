@@ -1,4 +1,5 @@
-// The result object behind nbg_rows_* (engine.cpp) and the stages over device rows (stages.cpp).
+// The result object behind nbg_rows_* (engine.cpp), the GO driver that builds it (go.cpp) and the
+// stages over device rows (stages.cpp).
 #pragma once
 #include <string>
 #include <unordered_map>

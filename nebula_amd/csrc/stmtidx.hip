@@ -1,7 +1,7 @@
 // The filtered adjacency of one (prepared GO statement, OVER type): the CSR rows restricted to the
 // edges that pass the statement's WHERE `col <cmp> const`, built once so that the statement's
 // final steps copy rows instead of re-reading the WHERE column and the failing edges' _dst on
-// every execution (engine.cpp go_launch substitutes it; the snapshot is immutable after finalize).
+// every execution (go.cpp go_launch substitutes it; the snapshot is immutable after finalize).
 //   pos = exclusive scan of the pass flags (the flags are computed inside the scan's input
 //         iterator and again by the scatter: no flag array), E + 1 entries, pos[E] = passing edges
 //   rp'[v] = pos[row_ptr[v]]            (nv + 1 entries)

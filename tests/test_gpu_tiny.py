@@ -1,4 +1,4 @@
-"""The single-launch path for tiny GO queries (kernels.hip k_go_tiny, engine.cpp go_launch).
+"""The single-launch path for tiny GO queries (kernels.hip k_go_tiny, go.cpp go_launch).
 
 A GO N STEPS (N <= 3, one OVER type, rows fetched to the host) whose walk bound — W_N of its
 starts, DevEdgeType::h_w2 / h_w3 — fits one workgroup runs as ONE launch: per-step sets in LDS,
