@@ -25,6 +25,7 @@
  *   nbg_yield                  ≙ YieldExecutor over piped rows (src/graph/YieldExecutor.cpp:178-282)
  *   nbg_fetch_vertices         ≙ FetchVerticesExecutor over piped rows or a vid list
  *       (src/graph/FetchVerticesExecutor.cpp:19-311, src/graph/FetchExecutor.cpp:14-131)
+ *   nbg_fetch_edges ≙ FetchEdgesExecutor (src/graph/FetchEdgesExecutor.cpp:17-384, src/graph/FetchExecutor.cpp:14-131, src/storage/QueryEdgePropsProcessor.cpp:17-101)
  *   nbg_get_neighbors          ≙ StorageServiceHandler::future_getBound → QueryBoundProcessor
  *       (src/storage/StorageServiceHandler.cpp:33-40, src/storage/QueryBoundProcessor.cpp:16-220)
  */
@@ -117,6 +118,17 @@ extern "C" {
  *   root of an expression a FLOAT prop is accepted and reads as its double, a DOUBLE column);
  *   more than NBG_MAX_YIELDS columns; a program over 256 instructions or over the interpreter's
  *   register limit; an input of 2^32 rows or more.
+ * nbg_fetch_edges (tests/test_gpu_fetch_edges.py holds one test per limit a GO result can reach; the
+ * mixed-kind key column, the missing CSR and the row count are guards no test reaches):
+ *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
+ *   an input whose row schema re-reads its columns (a misaligned or FLOAT column);
+ *   a key column (src, dst or rank) whose value kind differs between OVER types (col_kind == -1);
+ *   a YIELD that builds a string (concatenation, a cast to string, string functions);
+ *   a bare FLOAT prop (the result would carry a FLOAT column; below the root of an expression a
+ *   FLOAT prop is accepted and reads as its double, a DOUBLE column);
+ *   more than NBG_MAX_YIELDS columns; a program over 256 instructions or over the interpreter's
+ *   register limit; an input of 2^32 rows or more; an edge type without a device CSR (registered,
+ *   but no edge of it was loaded).
  * (A storage filter with a function call is E_INVALID_FILTER per part, as checkExp answers it,
  * QueryBaseProcessor.inl:172-290.)
  * Not limits: $- / $var input strings absent from the snapshot's dictionary, string functions
@@ -705,6 +717,98 @@ typedef struct {
 } nbg_fetch_request;
 int32_t nbg_fetch_vertices(nbg_engine* e, const nbg_rows* in, const nbg_fetch_request* req, nbg_rows** out);
 
+/* ---- piped FETCH PROP ON <edge> over a device-resident result (FetchEdgesExecutor) -------------
+ * `| FETCH PROP ON serve $-.src->$-.dst[@$-.rank] YIELD serve.start_year` over rows in HBM, and
+ * `FETCH PROP ON serve 100->200@0, 100->201` (FetchEdgesExecutor.cpp:17-384, FetchExecutor.cpp:14-131,
+ * QueryEdgePropsProcessor.cpp:17-101).  Input and output follow nbg_fetch_vertices' contract: `in`
+ * is a device-resident result of the same single engine (a GO result, or the output of nbg_group_by,
+ * nbg_order_by, nbg_set_op, nbg_yield, nbg_fetch_vertices or nbg_fetch_edges itself); it stays valid
+ * and unchanged.  `out` is an ordinary device-resident nbg_rows of one segment in a workspace of its
+ * own: every nbg_rows_* accessor works on it and it feeds every stage, nbg_fetch_vertices and
+ * nbg_fetch_edges too.  It carries no column names.  The call runs under the engine lock on the
+ * engine's stream; its scratch is released before it returns: 5 bytes per input row (a 4-byte edge
+ * index and a keep byte; 9 when a YIELD reads `_src', which keeps the source's 4-byte dense id), 32
+ * bytes per chunk of at most 2,048 rows (the 24-byte chunk list entry, a count and a base), a
+ * 16-byte state word pair and the compiled program; literal keys add their temporary input of 24
+ * bytes per key, and `distinct' adds nbg_set_op's UNION DISTINCT scratch beside the rows not yet
+ * de-duplicated.  A failed allocation is NBG_E_OUT_OF_MEMORY.  With in == NULL the evaluated keys
+ * `srcs' / `dsts' / `ranks' are uploaded into a temporary three-column result and take the same path.
+ *
+ * Rows: one result row per input row whose key is found; duplicates are kept (setupEdgeKeysFromRef
+ * keeps them without DISTINCT, :182-197).  A key (src, dst, rank) is found when src is a vertex of
+ * the snapshot, that vertex lives in the part the storage client asks (StorageClient::getEdgeProps
+ * clusters the keys by src: uint64(src) % num_parts + 1), and src's out-edges of the type hold an
+ * entry with that (rank, dst).  The latest version answers (collectEdgesProps takes the first key of
+ * the prefix scan, the newest write, :22-38); older versions are never read, and
+ * max_edge_returned_per_vertex does not apply (QueryEdgePropsProcessor has no cap).  A key that is
+ * not found yields no row and no error (FetchEdgesTest.nonExistEdge); when nothing is found the
+ * result is NBG_OK with zero rows.  rank_col == NULL (in == NULL: ranks == NULL) gives every key
+ * rank 0 (:187).
+ *
+ * Row order: the input's fetch order with the missing rows removed (the reference's order is per
+ * host and part, hence unspecified), so `ORDER BY | FETCH | LIMIT' is exact.  Under `distinct'
+ * the order is unspecified.
+ *
+ * distinct (YIELD DISTINCT): the result holds each distinct output row once (processResult's
+ * uniqResult, :322, :371-375); doubles compare as in nbg_set_op.  De-duplicating the keys first
+ * (EdgeKeyHashSet, :178-197, :204-255) is then redundant.
+ *
+ * Expressions: everything nbg_go's compiler accepts for one OVER type over the edge's props,
+ * `_src', `_dst', `_rank', `_type' and constants, with GO's results (`edge._type' is the edge's
+ * name, a STRING, as EdgeTypeExpression::eval has it).  A YIELD that is exactly `edge.prop' is
+ * copied without the interpreter; a constant YIELD is a kernel argument.
+ * Unspecified in the reference: an edge whose value does not decode.  There collectProps writes a
+ * short row the executor then misreads.  Here a YIELD that reads a schema prop of such an edge is an
+ * evaluation error (status 8); `_src', `_dst', `_rank' and `_type' of it still evaluate.
+ *
+ * Result schema: col_types follow FetchExecutor::prepareYield (FetchExecutor.cpp:35-47): a bare
+ * `edge.prop' takes the edge schema's field type, a root cast the cast's type, anything else the
+ * value's natural type.  `_src', `_dst', `_rank' and `_type' are no alias expressions there
+ * (Expression::isAliasExpression is kind_ == kAliasProp, Expressions.h:192-194; they have kinds of
+ * their own), and an edge schema has no field of those names, so they take the natural type: INT
+ * for the first three, STRING for `_type'.  String cells are dictionary codes; string constants
+ * outside the dictionary are carried as nbg_yield carries them.
+ *
+ * Statuses, in this order:
+ *  1. NBG_E_INVALID_ARGUMENT: a null argument; `in' host-only or of another engine; in != NULL
+ *     with a null src_col or dst_col; in == NULL with num_keys > 0 and null srcs or dsts;
+ *     expression bytes that do not decode.
+ *  2. NBG_E_UNSUPPORTED: a partitioned engine.
+ *  3. NBG_E_EXECUTION_ERROR: edge_type not registered ("edge schema not exist", :36-47); src_col,
+ *     dst_col or rank_col equal to `*' (:83-88).
+ *  4. NBG_E_SYNTAX_ERROR, for an empty input too (prepareYield runs before setupEdgeKeys): any `$^' /
+ *     `$$' node; any `$-' / `$var' node in a YIELD; an alias other than the edge's name
+ *     (FetchExecutor.cpp:50-68; FetchEdgesTest.syntaxError).  ("Only support single data source.",
+ *     EdgeKeyRef::varname, is the binding's to answer: the request carries column names only.)
+ *  5. Zero input rows or zero keys: NBG_OK and a zero-row result with one column per YIELD
+ *     (onEmptyInputs, FetchExecutor.cpp:99-107).
+ *  6. NBG_E_EXECUTION_ERROR: src_col, dst_col or rank_col (in that order) absent from
+ *     input_names, or a column whose kind is not INT or whose col_type is neither INT nor VID
+ *     ("Column `x' not found": getVIDs -> RowReader::getVid, which the rank column goes through
+ *     too, :158-176); no alias property anywhere in the YIELDs ("No props declared.", :270-274);
+ *     a prop the edge's latest schema lacks ("Get props failed", :280-283).
+ *  7. Device scope: see "Device limits" (NBG_E_UNSUPPORTED; the caller then fetches the keys and
+ *     runs the reference's path).
+ *  8. An evaluation error in a YIELD of a found row: NBG_E_EXECUTION_ERROR, no result (:355-359).
+ * Single engine only.  The join is a binary search of the sorted vid table per row, then one of
+ * the source's CSR row in the key's byte order (DESIGN.md "FETCH PROP ON <edge> over device rows"). */
+typedef struct {
+  const char* const* input_names;    /* names of `in`'s columns; unused when in == NULL             */
+  const char* src_col;               /* the `name' of `$-.name' / `$var.name' left of `->'          */
+  const char* dst_col;               /* ... right of `->'                                            */
+  const char* rank_col;              /* ... after `@'; NULL: no rank given, every key has rank 0     */
+  const int64_t* srcs;               /* in == NULL: the evaluated keys of `FETCH PROP ON e 1->2@0,..' */
+  const int64_t* dsts;
+  const int64_t* ranks;              /* NULL: all 0                                                  */
+  uint64_t num_keys;
+  int32_t edge_type;                 /* positive type of `ON <edge>' (the binding resolved the name) */
+  const uint8_t* const* yield_exprs; /* Expression::encode bytes per YIELD column                    */
+  const uint32_t* yield_lens;
+  int32_t num_yields;                /* 0: every column of the edge's latest schema, in schema order */
+  int32_t distinct;                  /* YIELD DISTINCT                                               */
+} nbg_fetch_edges_request;
+int32_t nbg_fetch_edges(nbg_engine* e, const nbg_rows* in, const nbg_fetch_edges_request* req, nbg_rows** out);
+
 /* ---- FIND SHORTEST | ALL PATH (FindPathExecutor semantics) ----------------------------- */
 typedef struct {
   const int64_t* from;           /* de-duplicated by the callee (VerticesClause::prepare)    */
@@ -854,7 +958,8 @@ typedef struct {
  * k_ob_copy (DESIGN.md "ORDER BY / LIMIT"), and nbg_set_op's: k_so_insert, k_so_probe, k_so_emit,
  * k_so_copy (DESIGN.md "Set operations over device rows"), and nbg_yield's: k_yr_filter,
  * k_yr_scan, k_yr_emit (DESIGN.md "YIELD over device rows"), and nbg_fetch_vertices':
- * k_fv_resolve, k_fv_emit (DESIGN.md "FETCH PROP over device rows"). */
+ * k_fv_resolve, k_fv_emit (DESIGN.md "FETCH PROP over device rows"), and nbg_fetch_edges':
+ * k_fe_resolve, k_fe_emit (DESIGN.md "FETCH PROP ON <edge> over device rows"). */
 /* ---- FIND PATH replica of a partitioned engine (replica.hip) ---------------------------------
  * A partitioned engine (num_gpus > 1) also builds, at nbg_finalize (collectively), a replica of
  * every rank's path CSRs (offsets, neighbour ids and vids, ranks; no property columns) when it fits

@@ -111,6 +111,13 @@ class nbg_fetch_request(C.Structure):
                 ("distinct", i32)]
 
 
+class nbg_fetch_edges_request(C.Structure):
+    _fields_ = [("input_names", P(C.c_char_p)), ("src_col", C.c_char_p), ("dst_col", C.c_char_p),
+                ("rank_col", C.c_char_p), ("srcs", P(i64)), ("dsts", P(i64)), ("ranks", P(i64)), ("num_keys", u64),
+                ("edge_type", i32), ("yield_exprs", P(P(u8))), ("yield_lens", P(u32)), ("num_yields", i32),
+                ("distinct", i32)]
+
+
 SET_UNION, SET_INTERSECT, SET_MINUS = 1, 2, 3
 SET_BY_NAME = {"UNION": SET_UNION, "INTERSECT": SET_INTERSECT, "MINUS": SET_MINUS}
 
@@ -158,6 +165,7 @@ SIGNATURES = [
     ("nbg_set_op", i32, [vp, vp, vp, P(nbg_set_request), P(vp)]),
     ("nbg_yield", i32, [vp, vp, P(nbg_yield_request), P(vp)]),
     ("nbg_fetch_vertices", i32, [vp, vp, P(nbg_fetch_request), P(vp)]),
+    ("nbg_fetch_edges", i32, [vp, vp, P(nbg_fetch_edges_request), P(vp)]),
     ("nbg_find_path", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_submit", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_wait", i32, [vp, P(vp)]),

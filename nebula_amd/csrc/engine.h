@@ -72,6 +72,7 @@ struct Engine {
   StageProf<SO_KINDS> so_prof;                       // nbg_set_op's kernels
   StageProf<YR_KINDS> yr_prof;                       // nbg_yield's kernels
   StageProf<FV_KINDS> fv_prof;                       // nbg_fetch_vertices' kernels
+  StageProf<FE_KINDS> fe_prof;                       // nbg_fetch_edges' kernels
   // pinned host blocks of fetched GO rows (nbg_rows_fetch), reused across queries
   std::mutex pinned_mu;
   std::vector<std::pair<size_t, void*>> pinned_free;
@@ -174,6 +175,7 @@ void for_stage_profs(Eng& E, F f) {
   f(kSoKernelNames, E.so_prof);   // nbg_set_op's (setops.hip)
   f(kYrKernelNames, E.yr_prof);   // nbg_yield's (yieldrows.hip)
   f(kFvKernelNames, E.fv_prof);   // nbg_fetch_vertices' (fetchrows.hip)
+  f(kFeKernelNames, E.fe_prof);   // nbg_fetch_edges' (fetchedges.hip)
 }
 
 int32_t engine_ready(Engine& E);   // workspace (+ partition buffers) after finalize / snapshot load

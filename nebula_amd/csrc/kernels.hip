@@ -1306,6 +1306,157 @@ hipError_t launch_fv_emit(const FvArgs& a, int nregs, unsigned grid, hipStream_t
   return hipGetLastError();
 }
 
+// ----------------------------------------------------------------------------- k_fe_resolve / k_fe_emit
+// nbg_fetch_edges' row kernels (driven by fetchedges.hip).  The program was compiled in the
+// ordinary per-edge mode for the one type of `ON <edge>`: `edge.prop` is OP_COL / OP_COLV over the
+// type's prop columns with EdgeCtx::j = the found edge's CSR index, `_src` reads d_vids at
+// EdgeCtx::v = the source's dense id.  Chunks and LDS registers as k_yr_*.
+
+// the eight little-endian bytes of a key field as memcmp reads them in the kvstore key: the
+// CSR's rows are sorted by (fe_key_image(rank), fe_key_image(dst)) as unsigned (loader.cpp)
+__device__ __forceinline__ uint64_t fe_key_image(int64_t x) {
+  uint64_t u = (uint64_t)x;
+  u = ((u & 0x00FF00FF00FF00FFull) << 8) | ((u >> 8) & 0x00FF00FF00FF00FFull);
+  u = ((u & 0x0000FFFF0000FFFFull) << 16) | ((u >> 16) & 0x0000FFFF0000FFFFull);
+  return (u << 32) | (u >> 32);
+}
+
+// per row: the key cells, the found edge's index (4 bytes: row_ptr is 32-bit), the source's dense
+// id where a YIELD reads _src, and a keep byte (src in d_vids and in the part the storage client
+// asks, (rank, dst) in its row); per chunk the kept count (a plain store, as k_fv_resolve).
+// Without a rank array every stored rank is 0: a key of another rank is a miss.  (A variant in
+// which only the first lane of a run of equal src searches the vid table and the others take its
+// result by wave shuffles measured slower and was deleted: DESIGN.md.)
+__global__ void __launch_bounds__(BLOCK) k_fe_resolve(FeArgs f) {
+  __shared__ uint32_t wcnt[WAVES];
+  const YrArgs& y = f.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t nv = f.nv;
+  const int64_t* __restrict__ scol = y.cols[f.src_col];
+  const int64_t* __restrict__ dcol = y.cols[f.dst_col];
+  const int64_t* __restrict__ rcol = f.rank_col >= 0 ? y.cols[f.rank_col] : nullptr;
+  for (uint32_t k = blockIdx.x; k < y.nchunks; k += gridDim.x) {
+    const uint64_t b = y.chunk[3 * k], len = y.chunk[3 * k + 1], lo = y.chunk[3 * k + 2];
+    uint32_t mine = 0;   // (wave-uniform)
+    for (uint64_t c0 = 0; c0 < len; c0 += BLOCK) {
+      const uint64_t i = c0 + threadIdx.x;
+      const bool valid = i < len;
+      bool found = false;
+      const int64_t src = valid ? scol[b + i] : 0;
+      uint64_t d = 0;
+      uint32_t r0 = 0, r1 = 0;     // the source's row of the CSR; empty: no such vertex, or not visible
+      if (valid) {
+        d = fv_lower_bound(f.vids, 0, nv, src);
+        if (d < nv && f.vids[d] == src && (!f.visible || f.visible[d])) {
+          r0 = f.row_ptr[d];
+          r1 = f.row_ptr[d + 1];
+        }
+        const int64_t dst = dcol[b + i], rk = rcol ? rcol[b + i] : 0;
+        uint32_t e = 0;
+        if (r0 < r1 && (f.rank || rk == 0)) {
+          const uint32_t end = r1;
+          uint32_t e0 = r0, e1 = end;
+          const uint64_t kr = fe_key_image(rk), kd = fe_key_image(dst);
+          while (e0 < e1) {   // the first entry of the row not below (rank, dst) in key byte order
+            const uint32_t mid = e0 + ((e1 - e0) >> 1);
+            const uint64_t mr = f.rank ? fe_key_image(f.rank[mid]) : 0ull, md = fe_key_image(f.dst_vid[mid]);
+            if (mr < kr || (mr == kr && md < kd)) e0 = mid + 1;
+            else e1 = mid;
+          }
+          e = e0;
+          found = e < end && f.dst_vid[e] == dst && (!f.rank || f.rank[e] == rk);
+        }
+        f.eidx[lo + i] = found ? e : 0u;
+        if (f.dense) f.dense[lo + i] = (uint32_t)(found ? d : 0);
+        y.keep[lo + i] = found;
+      }
+      mine += (uint32_t)__popcll(__ballot(found));
+    }
+    if (lane == 0) wcnt[wave] = mine;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t t = 0;
+      for (int w = 0; w < WAVES; ++w) t += wcnt[w];
+      y.ccount[k] = t;
+    }
+    __syncthreads();   // (wcnt is rewritten for the next chunk)
+  }
+}
+
+// k_fv_emit over the found rows with EdgeCtx{the edge's index, the source's dense id}; a column is
+// a register, the constant (-1), or prop column -2 - r of the found edge as it is (an evaluation
+// error where the edge's value did not decode, as OP_COLV).  CODE = false: the YIELDs are bare
+// props and constants only, so the interpreter is not instantiated (its registers and scratch
+// with it) and the copy runs at full occupancy.
+template <bool CODE>
+__global__ void __launch_bounds__(BLOCK) k_fe_emit(FeArgs f) {
+  extern __shared__ int64_t regs[];   // [nregs][BLOCK]
+  constexpr int STEPS = (int)(OB_CHUNK / BLOCK);
+  __shared__ uint32_t woff[STEPS * WAVES];
+  const YrArgs& y = f.y;
+  ExpandArgs a = yr_expand_args(y);
+  a.props = f.props;
+  a.dst_vid = f.dst_vid;
+  a.rank = f.rank;
+  a.valid = f.valid;
+  a.vids = f.vids;
+  bool bare = false;   // some column is a prop column as it is
+  for (int col = 0; col < y.ncols; ++col) bare = bare || y.yield_reg[col] <= -2;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  bool any_err = false;
+  for (uint32_t k = blockIdx.x; k < y.nchunks; k += gridDim.x) {
+    const uint64_t len = y.chunk[3 * k + 1], lo = y.chunk[3 * k + 2];   // len <= OB_CHUNK (no input cell is read here)
+    const int steps = (int)((len < OB_CHUNK ? len : OB_CHUNK) + BLOCK - 1) / BLOCK;         // <= STEPS
+    for (int s = 0; s < steps; ++s) {
+      const uint64_t i = (uint64_t)s * BLOCK + threadIdx.x;
+      const bool take = i < len && y.keep[lo + (i < len ? i : 0)];
+      const unsigned long long bal = __ballot(take);
+      if (lane == 0) woff[s * WAVES + wave] = (uint32_t)__popcll(bal);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      uint32_t total = 0;
+      for (int j = 0; j < steps * WAVES; ++j) {
+        const uint32_t c = woff[j];
+        woff[j] = total;
+        total += c;
+      }
+    }
+    __syncthreads();
+    const uint64_t base = y.cbase[k];
+    for (int s = 0; s < steps; ++s) {
+      const uint64_t i = (uint64_t)s * BLOCK + threadIdx.x;
+      const bool take = i < len && y.keep[lo + (i < len ? i : 0)];
+      const unsigned long long bal = __ballot(take);
+      if (!bal) continue;   // (wave-uniform)
+      const uint64_t slot = base + woff[s * WAVES + wave] + lane_rank(bal);
+      bool yerr = false;
+      uint32_t tbits = 0;
+      const EdgeCtx c{take ? (uint64_t)f.eidx[lo + i] : 0ull, (take && f.dense) ? f.dense[lo + i] : 0u};
+      if (CODE) run_program(y.prog, y.prog + y.code_len, 0, y.code_len, c, a, regs, take, yerr, tbits);
+      if (take && bare && f.valid && !f.valid[c.j]) yerr = true;
+      any_err = any_err || (take && yerr);
+      if (take && slot < y.cap)
+        for (int col = 0; col < y.ncols; ++col) {
+          const int r = y.yield_reg[col];
+          y.out[col][slot] = (CODE && r >= 0) ? regs[r * BLOCK + threadIdx.x] : r == -1 ? y.yield_const[col] : f.props[-2 - r][c.j];
+        }
+    }
+    __syncthreads();   // (woff is rewritten for the next chunk)
+  }
+  if (__ballot(any_err) && lane == 0) atomicOr(y.err, 1ull);
+}
+
+hipError_t launch_fe_resolve(const FeArgs& a, unsigned grid, hipStream_t s) {
+  hipLaunchKernelGGL(k_fe_resolve, dim3(grid), dim3(BLOCK), 0, s, a);
+  return hipGetLastError();
+}
+hipError_t launch_fe_emit(const FeArgs& a, int nregs, unsigned grid, hipStream_t s) {
+  if (a.y.code_len > 0) hipLaunchKernelGGL(k_fe_emit<true>, dim3(grid), dim3(BLOCK), (size_t)nregs * BLOCK * 8, s, a);
+  else hipLaunchKernelGGL(k_fe_emit<false>, dim3(grid), dim3(BLOCK), 0, s, a);
+  return hipGetLastError();
+}
+
 // ----------------------------------------------------------------------------- k_expand
 // FINALF: the final step with a FastProg program (no interpreter: fewer registers, 8 waves/SIMD)
 // FINALD: FINALF whose YIELDs are only _dst / constants; a tile's rows are stored after the NEXT

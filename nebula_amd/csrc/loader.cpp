@@ -115,9 +115,10 @@ static void stage_push(EdgeStage& st, int64_t src, int64_t dst, int64_t rank, ui
   }
   st.src.push_back(src);
   st.dst.push_back(dst);
-  if (!st.rank.empty()) st.rank.push_back(rank);
+  // (a type's first record may be the one that needs the column: n == 0 materialised nothing)
+  if (!st.rank.empty() || rank != 0) st.rank.push_back(rank);
   if (!st.verkey.empty()) st.verkey.push_back(verkey);
-  if (!st.part.empty()) st.part.push_back(part);
+  if (!st.part.empty() || part != hash_part(src, parts)) st.part.push_back(part);
 }
 
 int32_t Engine::load_part_kv(int32_t part, const uint8_t* kd, const uint64_t* ko, const uint8_t* vd,

@@ -940,6 +940,55 @@ hipError_t launch_fv_emit(const FvArgs& a, int nregs, unsigned grid, hipStream_t
 int32_t ws_fetch_vertices(Workspace* inw, const int64_t* host_vids, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
                           const FvPlan& plan, Workspace** outw, uint64_t* rows, StageProf<FV_KINDS>* prof, std::string* err);
 
+// ---- FETCH PROP ON <edge> over device rows (fetchedges.hip; FetchEdgesExecutor.cpp:17-384,
+// QueryEdgePropsProcessor.cpp:17-101).  The (src, dst[, rank]) columns are joined to the edge
+// indices of the type's out-CSR (k_fe_resolve: the vid table, then the source's row in key byte
+// order), the found rows are ranked (k_yr_scan) and the YIELDs are evaluated with EdgeCtx{the
+// edge's index, the source's dense id} (k_fe_emit), so `edge.prop`, `_dst`, `_src` and `_rank` are
+// the per-edge loads GO's programs use.
+struct FePlan {
+  YrPlan y;                         // no WHERE; yield_reg -2 - c: prop column c of the found edge as it is
+  int src_col = 0, dst_col = 1;     // the input columns holding the keys
+  int rank_col = -1;                // -1: no rank given, every key has rank 0
+  bool need_src = false;            // some YIELD reads _src (OP_SRC): the source's dense id is kept per row
+  int prop_cols = 0;                // distinct prop columns the YIELDs read, _dst and _rank counted (profiling bytes)
+  const int64_t* vids = nullptr;    // Snapshot::d_vids / nv / d_visible
+  uint64_t nv = 0;
+  const uint8_t* visible = nullptr;
+  const uint32_t* row_ptr = nullptr;        // DevEdgeType::row_ptr / dst_vid / rank / valid / d_props of the type
+  const int64_t* dst_vid = nullptr;
+  const int64_t* rank = nullptr;            // nullptr: every rank is 0
+  const uint8_t* valid = nullptr;           // nullptr: every value decoded
+  const int64_t* const* props = nullptr;
+};
+enum FeKernel { FE_K_RESOLVE = 0, FE_K_EMIT, FE_KINDS };   // (the scan between them is k_yr_scan, untimed here)
+extern const char* const kFeKernelNames[FE_KINDS];
+struct FeArgs {
+  YrArgs y;                         // keep / ccount / cbase always set; cols: the input's column bases
+  int src_col, dst_col, rank_col;
+  const int64_t* vids;
+  uint64_t nv;
+  const uint8_t* visible;           // nullptr: every vertex is visible
+  const uint32_t* row_ptr;
+  const int64_t* dst_vid;
+  const int64_t* rank;
+  const uint8_t* valid;
+  const int64_t* const* props;
+  uint32_t* eidx;                   // one edge index per logical row (read only where keep is set)
+  uint32_t* dense;                  // the source's dense id per logical row; nullptr: no YIELD reads _src
+};
+hipError_t launch_fe_resolve(const FeArgs& a, unsigned grid, hipStream_t s);
+hipError_t launch_fe_emit(const FeArgs& a, int nregs, unsigned grid, hipStream_t s);
+// Joins the key columns of the rows of `inw` listed by segs (inw == nullptr: the segs[0].second
+// keys at host_src / host_dst / host_rank (nullptr: all 0), uploaded into a temporary three-column
+// result) to the edges and projects the found rows into a fresh rows-only workspace on `stream`
+// (*outw; nullptr when no key is found) of *rows rows, in the input's order.  Synchronous; every
+// scratch allocation is released before it returns.  NBG_OK, NBG_E_EXECUTION_ERROR (an evaluation
+// error), NBG_E_OUT_OF_MEMORY or NBG_E_DEVICE.
+int32_t ws_fetch_edges(Workspace* inw, const int64_t* host_src, const int64_t* host_dst, const int64_t* host_rank,
+                       hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs, const FePlan& plan,
+                       Workspace** outw, uint64_t* rows, StageProf<FE_KINDS>* prof, std::string* err);
+
 // Query pipeline (all asynchronous on the workspace stream until ws_end_query):
 hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, const std::vector<TypeProgram>* progs,
                           uint64_t stmt_id);

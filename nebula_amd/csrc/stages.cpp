@@ -1,7 +1,7 @@
 // The stages over device-resident rows at the C ABI (include/nbg.h): nbg_group_by, nbg_order_by,
-// nbg_set_op, nbg_yield and nbg_fetch_vertices.  Each plans its request on the host, as its
-// executor in the reference checks it, and hands the plan to its driver (groupby.hip, orderby.hip,
-// setops.hip, yieldrows.hip, fetchrows.hip).
+// nbg_set_op, nbg_yield, nbg_fetch_vertices and nbg_fetch_edges.  Each plans its request on the
+// host, as its executor in the reference checks it, and hands the plan to its driver (groupby.hip,
+// orderby.hip, setops.hip, yieldrows.hip, fetchrows.hip, fetchedges.hip).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -1004,6 +1004,190 @@ int32_t nbg_fetch_vertices(nbg_engine* h, const nbg_rows* in, const nbg_fetch_re
   uint64_t n = 0;
   if (int32_t rc = ws_fetch_vertices(d.w, in ? nullptr : rq->vids, E.stream, d.segs, plan, &ow, &n, &E.fv_prof, &err)) return E.fail(rc, err);
   // ---- YIELD DISTINCT (processResult's uniqResult, :159, :221-228): one row per distinct output
+  // row, through nbg_set_op's row table: the UNION DISTINCT of the result's two halves
+  if (ow && rq->distinct && n > 1) {
+    RowsWs first;   // the result before DISTINCT
+    first.w = ow;
+    SoPlan sp;
+    sp.op = NBG_SET_UNION;
+    sp.distinct = 1;
+    sp.ncols = ny;
+    for (int c = 0; c < ny; ++c) sp.dbl[c] = res->kinds[0][c] == VK_DOUBLE;   // (-0.0 == 0.0, as nbg_set_op)
+    const uint64_t half = n / 2;
+    ow = nullptr;
+    if (int32_t rc = ws_set_op(first.w, first.w, E.stream, {{0, half}}, {{half, n - half}}, sp, &ow, &n, &E.so_prof, &err))
+      return E.fail(rc, err);
+  }
+  if (ow) adopt_rows(res.get(), ow, n, ny);
+  *out = res.release();
+  return NBG_OK;
+}
+
+// ============================================================================= FETCH PROP ON <edge>
+// FetchEdgesExecutor / FetchExecutor (src/graph/FetchEdgesExecutor.cpp:17-384,
+// src/graph/FetchExecutor.cpp:14-131) over a device-resident result; the kernels are in
+// fetchedges.hip and, beside the interpreter, kernels.hip.
+int32_t nbg_fetch_edges(nbg_engine* h, const nbg_rows* in, const nbg_fetch_edges_request* rq, nbg_rows** out) {
+  if (!h || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  // ---- 1. arguments
+  if (rq->num_yields < 0 || (rq->num_yields > 0 && (!rq->yield_exprs || !rq->yield_lens)))
+    return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null argument");
+  if (in) {
+    if (!rq->input_names || !rq->src_col || !rq->dst_col) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null argument");
+    if (int32_t rc = guard_rows(E, "FETCH", {in})) return rc;
+  } else if ((!rq->srcs || !rq->dsts) && rq->num_keys) {
+    return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: null key list");
+  }
+  if (!E.finalized) return E.fail(NBG_E_STATE, "engine not finalized");
+  const int nc = in ? in->ncols : 3;
+  std::vector<std::string> names;
+  if (!in) names = {"src", "dst", "rank"};
+  else if (int32_t rc = copy_input_names(E, "FETCH", rq->input_names, nc, &names)) return rc;
+  // the key columns, in the order setupEdgeKeysFromRef reads them
+  std::vector<std::string> key_cols = in ? std::vector<std::string>{rq->src_col, rq->dst_col} : std::vector<std::string>{"src", "dst", "rank"};
+  if (in && rq->rank_col) key_cols.emplace_back(rq->rank_col);
+  std::string err;
+  std::vector<std::unique_ptr<Node>> yields;
+  for (int y = 0; y < rq->num_yields; ++y) {
+    if (!rq->yield_exprs[y] || !rq->yield_lens[y]) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: an empty expression");
+    yields.push_back(decode_expr(rq->yield_exprs[y], rq->yield_lens[y], &err));
+    if (!yields.back()) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: " + err);
+  }
+  // ---- 2.
+  if (int32_t rc = guard_partitioned(E, "FETCH")) return rc;
+  // ---- 3. prepareClauses (:36-47), prepareEdgeKeys (:83-88)
+  const int32_t type = rq->edge_type;
+  auto eit = type > 0 ? E.edges.find(type) : E.edges.end();
+  const Schema* esc = eit == E.edges.end() ? nullptr : eit->second.latest();
+  if (!esc) return E.fail(NBG_E_EXECUTION_ERROR, "edge type " + std::to_string(type) + ": edge schema not exist.");
+  const std::string& edge_name = eit->second.name;
+  if (in)
+    for (const std::string& kc : key_cols)
+      if (kc == "*") return E.fail(NBG_E_EXECUTION_ERROR, "Can not use `*' to reference a vertex id column.");
+  // ---- no YIELD clause: every column of the latest schema, in order (FetchExecutor::setupColumns, :73-90)
+  if (!rq->num_yields)
+    for (const Column& col : esc->cols) {
+      auto n = std::make_unique<Node>();
+      n->kind = EK_ALIAS;
+      n->alias = edge_name;
+      n->prop = col.name;
+      yields.push_back(std::move(n));
+    }
+  const int ny = (int)yields.size();
+  // ---- 4. prepareYield (FetchExecutor.cpp:50-68), before setupEdgeKeys: diagnosed for an empty input too
+  FvRefs refs;
+  for (auto& y : yields) fv_refs(*y, &refs);
+  if (refs.graph) return E.fail(NBG_E_SYNTAX_ERROR, "tag.prop and edgetype.prop are supported in fetch sentence.");
+  if (refs.input) return E.fail(NBG_E_SYNTAX_ERROR, "`$-' and `$variable' not supported in fetch yet.");
+  for (auto& ap : refs.alias)
+    if (ap.first != edge_name)
+      return E.fail(NBG_E_SYNTAX_ERROR,
+                    "Near [" + ap.first + "." + ap.second + "], tag or edge should be declared in statement first.");
+  // ---- 5. no rows (onEmptyInputs, FetchExecutor.cpp:99-107): one column per YIELD
+  const uint64_t nin = in ? in->count : rq->num_keys;
+  if (!nin) {
+    *out = new_rows(E, std::min(ny, (int)MAX_YIELDS));
+    return NBG_OK;
+  }
+  // ---- 6. getVIDs -> RowReader::getVid per key column (:158-176): INT and VID columns only;
+  // getPropNames (:270-274); the storage request names a prop the schema lacks (:280-283)
+  int kcol[3] = {0, 1, in ? -1 : 2};
+  bool key_mixed = false;
+  std::string mixed_name;
+  if (in) {
+    const InputCols cols(in);
+    for (size_t k = 0; k < key_cols.size(); ++k) {
+      auto it = std::find(names.begin(), names.end(), key_cols[k]);
+      const int c = it == names.end() ? -1 : (int)(it - names.begin());
+      if (c < 0 || cols.kind[c] != VK_INT || (cols.type[c] != NBG_T_INT && cols.type[c] != NBG_T_VID))
+        return E.fail(NBG_E_EXECUTION_ERROR, "Column `" + key_cols[k] + "' not found");
+      if (cols.mixed[c] && !key_mixed) {
+        key_mixed = true;
+        mixed_name = key_cols[k];
+      }
+      kcol[k] = c;
+    }
+  }
+  auto key_prop = [](const std::string& p) { return p == "_src" || p == "_dst" || p == "_rank" || p == "_type"; };
+  if (refs.alias.empty()) return E.fail(NBG_E_EXECUTION_ERROR, "No props declared.");
+  for (auto& ap : refs.alias)
+    if (!key_prop(ap.second) && esc->find(ap.second) < 0) return E.fail(NBG_E_EXECUTION_ERROR, "Get props failed");
+  // ---- 7. device scope
+  if (in && (in->misaligned || in->float_col))
+    return E.fail(NBG_E_UNSUPPORTED, "FETCH: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (key_mixed) return E.fail(NBG_E_UNSUPPORTED, "FETCH: column `" + mixed_name + "' mixes value kinds");
+  if (ny > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "FETCH: more than NBG_MAX_YIELDS columns");
+  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "FETCH: the rows have no columns");
+  if (nin > 0xFFFFFFFFull) return E.fail(NBG_E_UNSUPPORTED, "FETCH: an input of 2^32 rows or more");
+  auto dit = E.snap.types.find(type);
+  if (dit == E.snap.types.end() || !dit->second.row_ptr || !dit->second.dst_vid || !dit->second.d_props || !E.snap.d_vids)
+    return E.fail(NBG_E_UNSUPPORTED, "FETCH: the edge type has no device CSR");
+  const DevEdgeType& dt = dit->second;
+  // ---- compile: the YIELDs in the per-edge mode of a GO over this one type, one program for every found row
+  const std::vector<int32_t> over{type};
+  CompileEnv cenv{type, &over, &E.edges, &E.snap.strings, dt.valid != nullptr, dt.rank != nullptr};
+  cenv.tags = &E.tags;
+  cenv.max_dict_len = E.refresh_max_dict_len();
+  ProgramBuilder pb;
+  FePlan plan;
+  plan.y.ncols = ny;
+  plan.src_col = kcol[0];
+  plan.dst_col = kcol[1];
+  plan.rank_col = kcol[2];
+  std::unique_ptr<nbg_rows> res(new_rows(E, ny));
+  ColTypeEnv tenv;
+  std::set<int32_t> pcols_read;
+  for (int y = 0; y < ny; ++y) {
+    const Node& n = *yields[y];
+    const int col = n.kind == EK_ALIAS ? esc->find(n.prop) : -1;
+    if (col >= 0) {   // a bare `edge.prop': the found edge's column as it is
+      if (col >= (int)dt.props.size() || col >= (int)dt.prop_kind.size())
+        return E.fail(NBG_E_UNSUPPORTED, "FETCH: the edge type has no device CSR");
+      plan.y.yield_reg[y] = -2 - col;
+      pcols_read.insert(col);
+      res->kinds[0][y] = dt.prop_kind[col];
+      res->col_types[y] = esc->cols[col].type;   // FetchExecutor::prepareYield, :37-42
+      if (res->col_types[y] == NBG_T_FLOAT) return E.fail(NBG_E_UNSUPPORTED, "FETCH: a bare FLOAT prop (a FLOAT result column)");
+      continue;
+    }
+    if (int32_t rc = compile_yield_column(E, "FETCH", n, cenv, tenv, pb, y, &plan.y, res.get())) return rc;   // :43-47
+  }
+  if (int32_t rc = finish_program(E, "FETCH", pb, &plan.y)) return rc;
+  bool reads_dst = false, reads_rank = false;
+  for (const Ins& i : plan.y.code) {
+    if (i.op == OP_COL || i.op == OP_COLV) pcols_read.insert(i.aux);
+    plan.need_src = plan.need_src || i.op == OP_SRC;
+    reads_dst = reads_dst || i.op == OP_DST;
+    reads_rank = reads_rank || (i.op == OP_RANK && dt.rank);
+  }
+  plan.prop_cols = (int)pcols_read.size() + reads_dst + reads_rank;
+  // ---- 8. the passes
+  DeviceInput d;
+  if (in) {
+    if (int32_t rc = device_input(E, "FETCH", in, &d)) return rc;
+  } else {   // the literal keys: ws_fetch_edges uploads them into a temporary three-column result
+    if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+    d.segs.emplace_back(0, nin);
+  }
+  plan.y.str = E.dev_strings();
+  plan.y.now_sec = (int64_t)time(nullptr);
+  plan.y.rand_seed = query_rand_seed();
+  plan.vids = E.snap.d_vids;
+  plan.nv = E.snap.nv;
+  plan.visible = E.snap.d_visible;
+  plan.row_ptr = dt.row_ptr;
+  plan.dst_vid = dt.dst_vid;
+  plan.rank = dt.rank;
+  plan.valid = dt.valid;
+  plan.props = dt.d_props;
+  Workspace* ow = nullptr;
+  uint64_t n = 0;
+  if (int32_t rc = ws_fetch_edges(d.w, in ? nullptr : rq->srcs, rq->dsts, rq->ranks, E.stream, d.segs, plan, &ow, &n, &E.fe_prof, &err))
+    return E.fail(rc, err);
+  // ---- YIELD DISTINCT (processResult's uniqResult, :322, :371-375): one row per distinct output
   // row, through nbg_set_op's row table: the UNION DISTINCT of the result's two halves
   if (ow && rq->distinct && n > 1) {
     RowsWs first;   // the result before DISTINCT

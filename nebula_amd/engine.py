@@ -482,6 +482,34 @@ class Engine:
         self._check(self.lib.nbg_fetch_vertices(self.h, handle, C.byref(req), C.byref(out)), "fetch_vertices")
         return DeviceRows(self, out)
 
+    def fetch_edges(self, rows_or_keys, input_names, src_col, dst_col, rank_col, edge_type, yields=(),
+                    distinct=False) -> DeviceRows:
+        """nbg_fetch_edges: ``| FETCH PROP ON <edge> $-.src_col->$-.dst_col[@$-.rank_col] YIELD [DISTINCT]
+        yields`` over a device-resident result (``rank_col`` None: every key has rank 0), or ``FETCH
+        PROP ON <edge> s->d@r, ...`` when ``rows_or_keys`` is a sequence of ``(src, dst, rank)``
+        triples (``input_names`` and the column names are then unused).  ``edge_type`` is the edge's
+        positive type; ``yields`` holds Expression::encode bytes per YIELD column; none means every
+        column of the edge's latest schema.  The result is a new DeviceRows with one row per input
+        row whose key is an edge, in the input's row order; the input stays valid and unchanged."""
+        bufs = [np.frombuffer(bytes(b), np.uint8).copy() for b in yields]
+        ptrs = (C.POINTER(C.c_uint8) * max(1, len(bufs)))(*[b.ctypes.data_as(C.POINTER(C.c_uint8)) for b in bufs])
+        lens = (C.c_uint32 * max(1, len(bufs)))(*[len(b) for b in bufs])
+        if isinstance(rows_or_keys, DeviceRows):
+            names = (C.c_char_p * max(1, len(input_names)))(*[n.encode() for n in input_names])
+            req = L.nbg_fetch_edges_request(names, src_col.encode(), dst_col.encode(),
+                                            None if rank_col is None else rank_col.encode(), None, None, None, 0,
+                                            int(edge_type), ptrs, lens, len(bufs), int(bool(distinct)))
+            handle = rows_or_keys.h
+        else:
+            keys = np.ascontiguousarray(np.asarray([tuple(k) for k in rows_or_keys], dtype=np.int64).reshape(-1, 3).T)
+            kptr = [keys[c].ctypes.data_as(C.POINTER(C.c_int64)) if keys.shape[1] else None for c in range(3)]
+            req = L.nbg_fetch_edges_request(None, None, None, None, kptr[0], kptr[1], kptr[2], keys.shape[1],
+                                            int(edge_type), ptrs, lens, len(bufs), int(bool(distinct)))
+            handle = None
+        out = C.c_void_p()
+        self._check(self.lib.nbg_fetch_edges(self.h, handle, C.byref(req), C.byref(out)), "fetch_edges")
+        return DeviceRows(self, out)
+
     def default_columns(self, etypes, over_all=False):
         """Edge types of a YIELD-less GO's `<edge>._dst` columns, in column order (OVER order;
         for OVER *, the response edge_schema's iteration order, GoExecutor.cpp:481-499)."""
