@@ -23,6 +23,8 @@
  *       src/graph/LimitExecutor.cpp:18-66)
  *   nbg_set_op                 ≙ SetExecutor (src/graph/SetExecutor.cpp:98-383)
  *   nbg_yield                  ≙ YieldExecutor over piped rows (src/graph/YieldExecutor.cpp:178-282)
+ *   nbg_yield_agg              ≙ YieldExecutor with aggregate functions and no GROUP BY
+ *       (src/graph/YieldExecutor.cpp:33-58, 178-282, AggregateFunction.h)
  *   nbg_fetch_vertices         ≙ FetchVerticesExecutor over piped rows or a vid list
  *       (src/graph/FetchVerticesExecutor.cpp:19-311, src/graph/FetchExecutor.cpp:14-131)
  *   nbg_fetch_edges ≙ FetchEdgesExecutor (src/graph/FetchEdgesExecutor.cpp:17-384, src/graph/FetchExecutor.cpp:14-131, src/storage/QueryEdgePropsProcessor.cpp:17-101)
@@ -99,6 +101,7 @@ extern "C" {
  * column, the differently spelt constants and the row count are guards no test reaches):
  *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
  *   any aggregate function (yield_funs[i] != NBG_AGG_NONE): whole-input aggregates without GROUP BY;
+ *   (nbg_yield_agg below is the call for those requests;)
  *   a WHERE or YIELD that builds a string (concatenation, a cast to string, string functions);
  *   any use other than a bare pass-through column of a string column that can hold strings outside
  *   the dictionary (a non-empty derived table, or a per-OVER-type constant outside the dictionary);
@@ -107,6 +110,23 @@ extern "C" {
  *   an input whose row schema re-reads its columns (a misaligned or FLOAT column);
  *   more than NBG_MAX_YIELDS columns after `$-.*' expansion; a program over 256 instructions or
  *   over the interpreter's register limit; an input of 2^32 rows or more.
+ * nbg_yield_agg (tests/test_gpu_yield_agg.py holds one test per limit a GO result can reach; the
+ * mixed-kind column, the string expression that builds no string and the row count are guards no
+ * test reaches):
+ *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
+ *   a column without a function that is not constant-foldable (`$-.w + 1' without a function, for
+ *   which the reference reports the last kept row's value; rand32(); now());
+ *   AVG over a TIMESTAMP-typed argument (the reference reads the wrong union member there);
+ *   an argument or WHERE that builds a string (concatenation, a cast to string, string functions);
+ *   MAX / MIN / COUNT_DISTINCT over a string argument that is anything but a constant or a bare
+ *   column, or over a bare string column that can hold strings outside the dictionary; any use
+ *   inside an expression of such a column;
+ *   a referenced column whose value kind differs between OVER types (col_kind == -1);
+ *   an input whose row schema re-reads its columns (a misaligned or FLOAT column);
+ *   more than NBG_MAX_YIELDS columns after `$-.*' expansion; a program over 256 instructions, or
+ *   whose registers and accumulator slots together are over the interpreter's register limit (a
+ *   slot per distinct (argument, fold): one for SUM / AVG, MAX, MIN and each BIT_*, two for STD);
+ *   an input of 2^32 rows or more.
  * nbg_fetch_vertices (tests/test_gpu_fetch.py holds one test per limit a GO result can reach; the
  * mixed-kind vid column, the missing tag tables and the row count are guards no test reaches):
  *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
@@ -639,6 +659,85 @@ typedef struct {
 } nbg_yield_request;
 int32_t nbg_yield(nbg_engine* e, const nbg_rows* in, const nbg_yield_request* req, nbg_rows** out);
 
+/* ---- piped YIELD with aggregate functions and no GROUP BY (YieldExecutor) ----------------------
+ * `| YIELD AVG($-.age), SUM($-.like), COUNT(*), 1+1` and
+ * `| YIELD COUNT(*), SUM($-.w * 2 + 1), MAX($-.w) WHERE $-.w < 50` over rows in HBM
+ * (YieldExecutor::checkAggFun / executeInputs, YieldExecutor.cpp:33-58, 178-282; the functions:
+ * AggregateFunction.h; YieldTest.AggCall).  The request is nbg_yield's struct with at least one
+ * yield_funs[i] != NBG_AGG_NONE; nbg_yield itself keeps answering such a request with
+ * NBG_E_UNSUPPORTED.  A request that references no `$-' / `$var' column at all is the reference's
+ * executeConstant / AggregateConstant: the binding answers it without this call.
+ *
+ * Input and output follow nbg_yield's contract: `in` is a device-resident result of the same
+ * single engine; it stays valid and unchanged.  `out` is an ordinary device-resident nbg_rows of
+ * one segment and ONE ROW in a workspace of its own, usable by every nbg_rows_* accessor and every
+ * stage.  The call runs under the engine lock on the engine's stream; its scratch (8 bytes per
+ * accumulator slot and 4 bytes per chunk of 2,048 rows, the compiled program; for each
+ * COUNT_DISTINCT over a column or an expression additionally nbg_yield's scratch, the argument of
+ * the kept rows as a one-column result, and nbg_set_op's scratch for its UNION DISTINCT) is
+ * released before it returns.  A failed allocation is NBG_E_OUT_OF_MEMORY.
+ *
+ * Statuses, in this order:
+ *  1. NBG_E_INVALID_ARGUMENT: nbg_yield's cases; a null yield_funs, or no yield_funs[i] !=
+ *     NBG_AGG_NONE at all (that request is nbg_yield's); a function outside
+ *     NBG_AGG_NONE..NBG_AGG_BIT_XOR.
+ *  2. NBG_E_UNSUPPORTED: a partitioned engine.
+ *  3. NBG_E_SYNTAX_ERROR: any `$^', `$$' or edge-property node (syntaxCheck, :116-122); a column
+ *     that is a bare `$-.x' / `$var.x' (after `$-.*' expansion) without a function (checkAggFun,
+ *     :33-58; YieldTest.AggCall).
+ *  4. NBG_E_EXECUTION_ERROR: both `$-' and `$var' referenced, or more than one variable name.
+ *  5. Zero input rows: NBG_OK and a zero-row result with one column per YIELD (nbg_yield's status
+ *     5: the reference dereferences a null schema there, so it stays unspecified).
+ *  6. A referenced column absent from input_names: NBG_E_EXECUTION_ERROR, with nbg_yield's
+ *     messages.  With duplicate names the first match wins.
+ *  7. Device scope: see "Device limits" (NBG_E_UNSUPPORTED).
+ *  8. Evaluation (NBG_E_EXECUTION_ERROR, no result): per row the WHERE is evaluated first and the
+ *     arguments only on the rows that pass.  An evaluation error in the WHERE of any row, or in an
+ *     argument on a passing row, fails the call.  An argument error on a row the WHERE rejects is
+ *     not an error.
+ *  9. The WHERE rejects every row of a non-empty input and the statement has a MAX, a MIN or a
+ *     column without a function: NBG_E_EXECUTION_ERROR ("Not Support: 0": a fresh function object
+ *     holds an empty ColumnValue, which InterimResult::getResultWriter refuses,
+ *     InterimResult.cpp:602-640).
+ *
+ * Value types (they differ from nbg_group_by's): the type a function sees is the one
+ * getOutputSchema gives the column (Collector::getSchema, TraverseExecutor.cpp:163-203): the static
+ * kind's own type (INT for every integer payload, so a VID or TIMESTAMP column reads as INT and
+ * AVG($-.d) over a VID column is defined here), or, for a cast at the root of the argument, the
+ * cast's type.  The only TIMESTAMP-typed argument is therefore a root `(timestamp)' cast.
+ *
+ * Functions (AggregateFunction.h), over the n >= 1 kept rows:
+ *   none            a column without a function and without `$-': the value (Group::apply keeps
+ *                   the last row's); on the device only a constant-foldable one; the constant's kind
+ *   COUNT           n, INT, for any argument, `*' included
+ *   COUNT_DISTINCT  the number of distinct values, INT; -0.0 and 0.0 are one value (ColumnValue ==,
+ *                   std::hash<double>); NaNs count by their bits: equal bits are one value (the
+ *                   reference counts every NaN row, no NaN being equal to itself); a constant or `*': 1
+ *   SUM             INT / TIMESTAMP: wrapping int64 of that type; DOUBLE: double; BOOL / STRING: INT 0
+ *   AVG             INT: double(wrapped sum) / n; DOUBLE: sum / n; BOOL / STRING: 0.0; TIMESTAMP: a
+ *                   device limit
+ *   MAX / MIN       the argument's type and order, exactly as nbg_group_by documents them: signed
+ *                   int64; doubles by the IEEE total-order image, NaNs included, either sign over
+ *                   zeros; false < true; dictionary strings by code
+ *   STD             INT / DOUBLE: sqrt(sum((x - avg)^2) / n), DOUBLE; anything else (TIMESTAMP
+ *                   included: Stdev::apply collects nothing): INT 0
+ *   BIT_AND / BIT_OR / BIT_XOR   INT-typed arguments only; anything else: INT 0
+ * col_types are the result value's type (schema->appendCol(name, val.getType()), :260-278).
+ * Arguments whose expressions are equal share one evaluation and their accumulators.
+ *
+ * The WHERE rejects every row of a non-empty input: one row of each fresh function object's
+ * getResult: COUNT and COUNT_DISTINCT 0; SUM INT 0, whatever the argument's type; STD and BIT_* INT
+ * 0; AVG a DOUBLE NaN (0.0 / 0; payload and sign unspecified).  With a MAX, a MIN or a column
+ * without a function it is status 9.  So the result's kinds are decided after the kept count is
+ * known.
+ *
+ * Repeatability: a chunk's partial results depend on its rows alone, and they are folded in an
+ * order the number of chunks alone decides, whatever the grid and the scheduling: two calls on the
+ * same nbg_rows give bit-identical doubles.  The same rows in another segmentation (after an
+ * nbg_order_by, say) may differ in the last bits of a double SUM / AVG / STD.
+ * Single engine only. */
+int32_t nbg_yield_agg(nbg_engine* e, const nbg_rows* in, const nbg_yield_request* req, nbg_rows** out);
+
 /* ---- piped FETCH PROP ON <tag> over a device-resident result (FetchVerticesExecutor) ----------
  * `| FETCH PROP ON player $-.id YIELD player.name, player.age` over rows in HBM
  * (FetchVerticesExecutor.cpp:19-311, FetchExecutor.cpp:14-131).  Input and output follow
@@ -960,6 +1059,8 @@ typedef struct {
  * k_yr_scan, k_yr_emit (DESIGN.md "YIELD over device rows"), and nbg_fetch_vertices':
  * k_fv_resolve, k_fv_emit (DESIGN.md "FETCH PROP over device rows"), and nbg_fetch_edges':
  * k_fe_resolve, k_fe_emit (DESIGN.md "FETCH PROP ON <edge> over device rows"). */
+/* ... and nbg_yield_agg's: k_ya_reduce, k_ya_finish (DESIGN.md "Aggregate YIELD over device rows");
+ * its COUNT_DISTINCT columns are counted under nbg_yield's and nbg_set_op's kernels. */
 /* ---- FIND PATH replica of a partitioned engine (replica.hip) ---------------------------------
  * A partitioned engine (num_gpus > 1) also builds, at nbg_finalize (collectively), a replica of
  * every rank's path CSRs (offsets, neighbour ids and vids, ranks; no property columns) when it fits

@@ -164,6 +164,7 @@ SIGNATURES = [
     ("nbg_order_by", i32, [vp, vp, P(nbg_order_request), P(vp)]),
     ("nbg_set_op", i32, [vp, vp, vp, P(nbg_set_request), P(vp)]),
     ("nbg_yield", i32, [vp, vp, P(nbg_yield_request), P(vp)]),
+    ("nbg_yield_agg", i32, [vp, vp, P(nbg_yield_request), P(vp)]),
     ("nbg_fetch_vertices", i32, [vp, vp, P(nbg_fetch_request), P(vp)]),
     ("nbg_fetch_edges", i32, [vp, vp, P(nbg_fetch_edges_request), P(vp)]),
     ("nbg_find_path", i32, [vp, P(nbg_path_request), P(vp)]),

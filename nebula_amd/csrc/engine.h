@@ -71,6 +71,7 @@ struct Engine {
   StageProf<OB_KINDS> ob_prof;                       // nbg_order_by's kernels (nbg_profile mode 1)
   StageProf<SO_KINDS> so_prof;                       // nbg_set_op's kernels
   StageProf<YR_KINDS> yr_prof;                       // nbg_yield's kernels
+  StageProf<YA_KINDS> ya_prof;                       // nbg_yield_agg's kernels
   StageProf<FV_KINDS> fv_prof;                       // nbg_fetch_vertices' kernels
   StageProf<FE_KINDS> fe_prof;                       // nbg_fetch_edges' kernels
   // pinned host blocks of fetched GO rows (nbg_rows_fetch), reused across queries
@@ -176,6 +177,7 @@ void for_stage_profs(Eng& E, F f) {
   f(kYrKernelNames, E.yr_prof);   // nbg_yield's (yieldrows.hip)
   f(kFvKernelNames, E.fv_prof);   // nbg_fetch_vertices' (fetchrows.hip)
   f(kFeKernelNames, E.fe_prof);   // nbg_fetch_edges' (fetchedges.hip)
+  f(kYaKernelNames, E.ya_prof);   // nbg_yield_agg's (yieldagg.hip)
 }
 
 int32_t engine_ready(Engine& E);   // workspace (+ partition buffers) after finalize / snapshot load

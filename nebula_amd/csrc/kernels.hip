@@ -31,6 +31,7 @@
 #include <cstring>
 #include <vector>
 
+#include "aggops.h"
 #include "stage.h"
 #include "ws.h"
 
@@ -1164,6 +1165,103 @@ hipError_t launch_yr_filter(const YrArgs& a, int nregs, unsigned grid, hipStream
 }
 hipError_t launch_yr_emit(const YrArgs& a, int nregs, unsigned grid, hipStream_t s) {
   hipLaunchKernelGGL(k_yr_emit, dim3(grid), dim3(BLOCK), (size_t)nregs * BLOCK * 8, s, a);
+  return hipGetLastError();
+}
+
+// ----------------------------------------------------------------------------- k_ya_reduce
+// nbg_yield_agg's row kernel (driven by yieldagg.hip): k_yr_filter's WHERE and k_yr_emit's argument
+// code per 256-row step, then every kept lane folds its values into the slots' accumulators.  The
+// accumulators are [nslots][BLOCK] x 8 B of dynamic LDS behind the registers (the slot count is a
+// run-time value: no per-thread array).  Per chunk and slot one wave butterfly and one combine of
+// the waves in wave order, then a plain store of partial[slot][chunk] and of the chunk's kept
+// count: no atomics but the error word, and a chunk's partial depends on its rows alone.  Whether
+// a lane's row was kept decides what enters an accumulator, never the value.
+__device__ __forceinline__ uint64_t ya_value(const YaSlot& sl, uint64_t v, double mean) {
+  switch (sl.op) {
+    case YA_MAX: case YA_MIN: return ord_image(v, sl.dbl);
+    case YA_SQ: {
+      const double x = sl.dbl ? __longlong_as_double((long long)v) : (double)(int64_t)v;
+      const double d = __dsub_rn(x, mean);
+      return (uint64_t)__double_as_longlong(__dmul_rn(d, d));
+    }
+    default: return v;
+  }
+}
+
+// INTERP = false: the request has no code at all (no WHERE; bare columns and constants under the
+// functions), so the kernel is built without the interpreter and its registers.
+template <bool INTERP>
+__global__ void __launch_bounds__(BLOCK) k_ya_reduce(YaArgs g) {
+  extern __shared__ int64_t regs[];   // [nregs][BLOCK] registers, then [nslots][BLOCK] accumulators
+  __shared__ uint64_t wpart[WAVES];
+  __shared__ uint32_t wcnt[WAVES];
+  const YrArgs& y = g.y;
+  uint64_t* acc = reinterpret_cast<uint64_t*>(regs) + (size_t)(INTERP ? g.nregs : 0) * BLOCK;
+  const ExpandArgs a = yr_expand_args(y);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  bool any_err = false;
+  for (uint32_t k = blockIdx.x; k < y.nchunks; k += gridDim.x) {
+    const uint64_t b = y.chunk[3 * k], len = y.chunk[3 * k + 1];
+    for (int s = 0; s < g.nslots; ++s)
+      if (ya_in_pass(g.slot[s].op, g.pass)) acc[s * BLOCK + threadIdx.x] = ya_identity(g.slot[s].op);
+    uint32_t mine = 0;   // (wave-uniform)
+    for (uint64_t c0 = 0; c0 < len; c0 += BLOCK) {
+      const uint64_t i = c0 + threadIdx.x;
+      const bool valid = i < len;
+      const EdgeCtx c{b + (valid ? i : 0), 0u};
+      bool take = valid;
+      if constexpr (INTERP) {
+        // the WHERE on every row, then the arguments on the rows it keeps (one call site: the
+        // interpreter is inlined once)
+#pragma unroll 1
+        for (int part = 0; part < 2; ++part) {
+          const int pc0 = part ? y.where_len : 0, pc1 = part ? y.code_len : y.where_len;
+          if (part && !__ballot(take)) break;   // (wave-uniform)
+          if (pc0 == pc1) continue;
+          bool perr = false;
+          uint32_t tbits = 0;
+          run_program(y.prog, y.prog + y.code_len, pc0, pc1, c, a, regs, take, perr, tbits);
+          any_err = any_err || (take && perr);
+          if (!part) take = take && !perr && regs[y.where_reg * BLOCK + threadIdx.x] != 0;
+        }
+      }
+      mine += (uint32_t)__popcll(__ballot(take));
+      if (take)
+        for (int s = 0; s < g.nslots; ++s) {
+          const YaSlot sl = g.slot[s];
+          if (!ya_in_pass(sl.op, g.pass)) continue;
+          uint64_t v = (uint64_t)sl.bits;
+          if (INTERP && sl.src >= 0) v = (uint64_t)regs[sl.src * BLOCK + threadIdx.x];
+          else if (sl.src <= -2) v = (uint64_t)y.cols[-2 - sl.src][c.j];
+          const int at = s * BLOCK + threadIdx.x;
+          acc[at] = ya_combine(sl.op, acc[at], ya_value(sl, v, sl.op == YA_SQ ? g.mean[s] : 0.0));
+        }
+    }
+    if (g.pass == 0) {
+      if (lane == 0) wcnt[wave] = mine;
+      __syncthreads();
+      if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < WAVES; ++w) t += wcnt[w];
+        y.ccount[k] = t;
+      }
+      __syncthreads();   // (wcnt is rewritten for the next chunk)
+    }
+    for (int s = 0; s < g.nslots; ++s) {
+      const uint8_t op = g.slot[s].op;
+      if (!ya_in_pass(op, g.pass)) continue;   // (uniform over the workgroup)
+      const uint64_t t = ya_block_reduce(op, acc[s * BLOCK + threadIdx.x], wpart);
+      if (threadIdx.x == 0) g.partial[(size_t)s * y.nchunks + k] = t;
+    }
+  }
+  if (__ballot(any_err) && lane == 0) atomicOr(y.err, 1ull);
+}
+
+hipError_t launch_ya_reduce(const YaArgs& a, unsigned grid, hipStream_t s) {
+  if (a.y.code_len > 0)
+    hipLaunchKernelGGL(k_ya_reduce<true>, dim3(grid), dim3(BLOCK), (size_t)(a.nregs + a.nslots) * BLOCK * 8, s, a);
+  else
+    hipLaunchKernelGGL(k_ya_reduce<false>, dim3(grid), dim3(BLOCK), (size_t)a.nslots * BLOCK * 8, s, a);
   return hipGetLastError();
 }
 

@@ -899,6 +899,77 @@ hipError_t launch_yr_emit(const YrArgs& a, int nregs, unsigned grid, hipStream_t
 int32_t ws_yield_rows(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
                       const YrPlan& plan, Workspace** outw, uint64_t* rows, StageProf<YR_KINDS>* prof, std::string* err);
 
+// ---- YIELD with aggregates and no GROUP BY over device rows (yieldagg.hip; YieldExecutor.cpp:33-58,
+// :178-282, AggregateFunction.h).  One program (WHERE first, then one register per distinct
+// argument expression) and the request compiled to accumulator slots and one emit rule per column.
+enum YaOp : uint8_t {
+  YA_SUM_I = 0, YA_SUM_D, YA_MAX, YA_MIN, YA_AND, YA_OR, YA_XOR,
+  YA_SQ,         // second pass: sum of (x - avg)^2, avg from slot `ref` and the kept count
+};
+enum YaEmit : uint8_t {
+  YE_CONST = 0,  // `bits`
+  YE_COUNT,      // the kept count
+  YE_SLOT,       // the slot as it stands (sums, bit folds)
+  YE_ORD_I,      // MAX / MIN of an integer-ordered argument: the slot's order-preserving image back
+  YE_ORD_D,      // ... of a DOUBLE argument
+  YE_AVG_I,      // double(int64 slot) / count
+  YE_AVG_D,      // double slot / count
+  YE_AVG_0,      // AVG over a BOOL / STRING argument: 0.0
+  YE_STD,        // sqrt(slot / count)
+};
+struct YaSlot {
+  uint8_t op;       // YaOp
+  uint8_t dbl;      // the value is a double (ordering, YA_SQ's conversion)
+  uint8_t ref;      // YA_SQ: the slot holding the sum (a double sum when `dbl`, else int64)
+  int32_t src;      // a register (>= 0); -1: the constant `bits`; -2 - c: input column c as it is
+  int64_t bits;
+};
+struct YaOut {
+  uint8_t emit;     // YaEmit
+  uint8_t slot;
+  int64_t bits;     // YE_CONST
+};
+constexpr int YA_MAX_SLOTS = 2 * MAX_YIELDS;
+struct YaDistinct {                 // one COUNT_DISTINCT column over a non-constant argument
+  YrPlan y;                         // the WHERE and the argument as one YIELD column (ws_yield_rows)
+  int out = 0;                      // the result column
+  uint8_t dbl = 0;                  // -0.0 and 0.0 are one value
+};
+struct YaPlan {
+  YrPlan y;                         // ncols = 0; the code after the WHERE computes the arguments
+  int nslots = 0;
+  YaSlot slot[YA_MAX_SLOTS] = {};
+  int nout = 0;
+  YaOut out[MAX_YIELDS] = {};
+  bool has_sq = false;              // some STD: the second pass runs
+  bool none = false;                // the WHERE is constant false: no row is kept, no row is read
+  int arg_cols = 0;                 // distinct input columns the arguments read (profiling bytes)
+  std::vector<YaDistinct> distinct;
+};
+// nbg_profile_read's aggregate-YIELD entries (kYaKernelNames), timed while nbg_profile mode 1 is on
+enum YaKernel { YA_K_REDUCE = 0, YA_K_FINISH, YA_KINDS };
+extern const char* const kYaKernelNames[YA_KINDS];
+struct YaArgs {
+  YrArgs y;                         // keep / ccount: ccount[k] = chunk k's kept rows (pass 0)
+  const YaSlot* slot;
+  int nslots, nregs;
+  int pass;                         // 0: every slot but YA_SQ; 1: the YA_SQ slots
+  uint64_t* partial;                // [nslots][nchunks]: chunk k's fold of slot s, a plain store
+  const double* mean;               // [nslots]: pass 1, the mean of each YA_SQ slot (k_ya_finish)
+};
+// k_ya_reduce sits beside the interpreter (kernels.hip); yieldagg.hip drives it.
+hipError_t launch_ya_reduce(const YaArgs& a, unsigned grid, hipStream_t s);
+// Reduces the rows of `inw` listed by segs (first row, rows) into a fresh rows-only workspace of
+// one row on `stream` (*outw).  *kept: the rows the WHERE kept; with none the row holds the empty
+// aggregates (0, and NaN for an AVG) and the caller decides what that means.  The COUNT_DISTINCT
+// columns go through ws_yield_rows and ws_set_op (their profiles: yr_prof, so_prof).  Synchronous;
+// every scratch allocation is released before it returns.  NBG_OK, NBG_E_EXECUTION_ERROR (an
+// evaluation error), NBG_E_UNSUPPORTED (registers and slots past the LDS), NBG_E_OUT_OF_MEMORY or
+// NBG_E_DEVICE.
+int32_t ws_yield_agg(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
+                     const YaPlan& plan, Workspace** outw, uint64_t* kept, StageProf<YA_KINDS>* prof,
+                     StageProf<YR_KINDS>* yr_prof, StageProf<SO_KINDS>* so_prof, std::string* err);
+
 // ---- FETCH PROP ON <tag> over device rows (fetchrows.hip; FetchVerticesExecutor.cpp:19-311).  The
 // vid column is joined to the dense vertex ids (k_fv_resolve), the found rows are ranked
 // (k_yr_scan) and the YIELDs are evaluated with EdgeCtx::v = the row's dense id (k_fv_emit), so

@@ -1,7 +1,7 @@
 // The stages over device-resident rows at the C ABI (include/nbg.h): nbg_group_by, nbg_order_by,
-// nbg_set_op, nbg_yield, nbg_fetch_vertices and nbg_fetch_edges.  Each plans its request on the
-// host, as its executor in the reference checks it, and hands the plan to its driver (groupby.hip,
-// orderby.hip, setops.hip, yieldrows.hip, fetchrows.hip, fetchedges.hip).
+// nbg_set_op, nbg_yield, nbg_yield_agg, nbg_fetch_vertices and nbg_fetch_edges.  Each plans its
+// request on the host, as its executor in the reference checks it, and hands the plan to its driver
+// (groupby.hip, orderby.hip, setops.hip, yieldrows.hip, yieldagg.hip, fetchrows.hip, fetchedges.hip).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -650,25 +650,36 @@ void yr_refs(const Node& n, YrRefs* r) {
     if (k) yr_refs(*k, r);
 }
 
-}  // namespace
+// Statuses 1 to 6, which nbg_yield and nbg_yield_agg check alike (`agg_call': the latter, whose
+// request must name a function)
+struct YieldFront {
+  std::vector<std::string> names;
+  std::unique_ptr<Node> where;
+  std::vector<std::unique_ptr<Node>> yields;   // after `$-.*' / `$var.*' expansion
+  std::vector<int32_t> funs;
+  YrRefs refs;
+  bool agg = false;    // some function
+  bool done = false;   // status 5: *out holds the zero-row result
+  int find_col(const std::string& n) const {   // getFieldIndex: the first column of that name
+    auto it = std::find(names.begin(), names.end(), n);
+    return it == names.end() ? -1 : (int)(it - names.begin());
+  }
+};
 
-int32_t nbg_yield(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq, nbg_rows** out) {
-  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
-  *out = nullptr;
-  Engine& E = h->e;
-  std::lock_guard<std::mutex> lg(E.mu);
+int32_t yield_front(Engine& E, const nbg_rows* in, const nbg_yield_request* rq, bool agg_call, YieldFront* F,
+                    nbg_rows** out) {
   // ---- 1. arguments
   if (rq->num_yields < 1) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: no YIELD column");
   if (!rq->input_names || !rq->yield_exprs || !rq->yield_lens) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: null argument");
+  if (agg_call && !rq->yield_funs) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: null argument");
   if (int32_t rc = guard_rows(E, "YIELD", {in})) return rc;
   const int nc = in->ncols;
-  std::vector<std::string> names;
+  std::vector<std::string>& names = F->names;
   if (int32_t rc = copy_input_names(E, "YIELD", rq->input_names, nc, &names)) return rc;
   std::string err;
-  std::unique_ptr<Node> where;
   if (rq->where && rq->where_len) {
-    where = decode_expr(rq->where, rq->where_len, &err);
-    if (!where) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: WHERE: " + err);
+    F->where = decode_expr(rq->where, rq->where_len, &err);
+    if (!F->where) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: WHERE: " + err);
   }
   std::vector<std::unique_ptr<Node>> given;
   for (int y = 0; y < rq->num_yields; ++y) {
@@ -677,14 +688,16 @@ int32_t nbg_yield(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq
     if (!given.back()) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: " + err);
     if (rq->yield_funs && (rq->yield_funs[y] < NBG_AGG_NONE || rq->yield_funs[y] > NBG_AGG_BIT_XOR))
       return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: unknown function");
+    F->agg = F->agg || (rq->yield_funs && rq->yield_funs[y] != NBG_AGG_NONE);
   }
+  if (agg_call && !F->agg) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: no aggregate function (the request is nbg_yield's)");
   // ---- 2.
   if (int32_t rc = guard_partitioned(E, "YIELD")) return rc;
   // ---- `$-.*' / `$var.*' (YieldClauseWrapper::prepare): every input column, in order
-  std::vector<std::unique_ptr<Node>> yields;
-  std::vector<int32_t> funs;
-  YrRefs refs;
-  if (where) yr_refs(*where, &refs);
+  std::vector<std::unique_ptr<Node>>& yields = F->yields;
+  std::vector<int32_t>& funs = F->funs;
+  YrRefs& refs = F->refs;
+  if (F->where) yr_refs(*F->where, &refs);
   for (int y = 0; y < rq->num_yields; ++y) {
     Node& n = *given[y];
     const int32_t f = rq->yield_funs ? rq->yield_funs[y] : NBG_AGG_NONE;
@@ -707,9 +720,7 @@ int32_t nbg_yield(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq
   }
   const int ny = (int)yields.size();
   // ---- 3. checkAggFun (:33-58), syntaxCheck (:116-122)
-  bool agg = false;
-  for (int32_t f : funs) agg = agg || f != NBG_AGG_NONE;
-  if (agg)
+  if (F->agg)
     for (int y = 0; y < ny; ++y)
       if ((yields[y]->kind == EK_INPUT || yields[y]->kind == EK_VAR) && funs[y] == NBG_AGG_NONE)
         return E.fail(NBG_E_SYNTAX_ERROR,
@@ -722,17 +733,64 @@ int32_t nbg_yield(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq
   // ---- 5. no rows: one column per YIELD
   if (!in->count) {
     *out = new_rows(E, std::min(ny, (int)MAX_YIELDS));
+    F->done = true;
     return NBG_OK;
   }
   // ---- 6. getOutputSchema (:298-316): getFieldIndex, the first column of that name
-  auto find_col = [&](const std::string& n) {
-    auto it = std::find(names.begin(), names.end(), n);
-    return it == names.end() ? -1 : (int)(it - names.begin());
-  };
   for (const std::string& p : refs.props)
-    if (find_col(p) < 0)
+    if (F->find_col(p) < 0)
       return E.fail(NBG_E_EXECUTION_ERROR,
                     "column `" + p + "' not exist in " + (refs.vars.empty() ? "input." : "variable."));
+  return NBG_OK;
+}
+
+// The WHERE into the program: asBool of its value in plan->where_reg, or, when it folds to a
+// constant, whether that is false (no code).  Its registers are dead once its value is read.
+int32_t compile_where(Engine& E, const Node& where, const CompileEnv& cenv, ProgramBuilder& pb, YrPlan* plan,
+                      bool* where_false) {
+  Compiled c;
+  std::string err;
+  if (int32_t rc = compile_expr(where, cenv, pb, &c, &err)) return E.fail(rc, "YIELD: " + err);
+  if (c.is_const) {
+    bool tv;
+    switch (c.kind) {   // Expression::asBool
+      case VK_STRING: tv = c.const_str.empty(); break;
+      case VK_DOUBLE: { double d; memcpy(&d, &c.const_bits, 8); tv = d != 0.0; break; }
+      default: tv = c.const_bits != 0;
+    }
+    *where_false = !tv;
+    pb.code.clear();
+  } else {
+    const int r = c.reg;
+    if (c.kind == VK_INT) pb.code.push_back(Ins{OP_TRUTHY_I, (uint8_t)r, (uint8_t)r, 0, 0, 0});
+    else if (c.kind == VK_DOUBLE) pb.code.push_back(Ins{OP_TRUTHY_F, (uint8_t)r, (uint8_t)r, 0, 0, 0});
+    else if (c.kind == VK_STRING)
+      pb.code.push_back(Ins{OP_TRUTHY_S, (uint8_t)r, (uint8_t)r, 0, 0, string_code(E.snap.strings, "")});
+    plan->where_len = (int)pb.code.size();
+    plan->where_reg = r;
+  }
+  pb.next_reg = 0;
+  return NBG_OK;
+}
+
+}  // namespace
+
+int32_t nbg_yield(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq, nbg_rows** out) {
+  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  // ---- 1. to 6.
+  YieldFront F;
+  if (int32_t rc = yield_front(E, in, rq, false, &F, out)) return rc;
+  if (F.done) return NBG_OK;
+  const int nc = in->ncols, ny = (int)F.yields.size();
+  const std::vector<std::string>& names = F.names;
+  const std::unique_ptr<Node>& where = F.where;
+  const std::vector<std::unique_ptr<Node>>& yields = F.yields;
+  const bool agg = F.agg;
+  auto find_col = [&](const std::string& n) { return F.find_col(n); };
+  std::string err;
   // ---- 7. device scope
   if (agg) return E.fail(NBG_E_UNSUPPORTED, "YIELD: aggregate functions without GROUP BY");
   if (in->misaligned || in->float_col)
@@ -773,29 +831,8 @@ int32_t nbg_yield(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq
   YrPlan plan;
   plan.ncols = ny;
   bool where_false = false;
-  if (where) {
-    Compiled c;
-    if (int32_t rc = compile_expr(*where, cenv, pb, &c, &err)) return E.fail(rc, "YIELD: " + err);
-    if (c.is_const) {
-      bool tv;
-      switch (c.kind) {   // Expression::asBool
-        case VK_STRING: tv = c.const_str.empty(); break;
-        case VK_DOUBLE: { double d; memcpy(&d, &c.const_bits, 8); tv = d != 0.0; break; }
-        default: tv = c.const_bits != 0;
-      }
-      where_false = !tv;
-      pb.code.clear();
-    } else {
-      const int r = c.reg;
-      if (c.kind == VK_INT) pb.code.push_back(Ins{OP_TRUTHY_I, (uint8_t)r, (uint8_t)r, 0, 0, 0});
-      else if (c.kind == VK_DOUBLE) pb.code.push_back(Ins{OP_TRUTHY_F, (uint8_t)r, (uint8_t)r, 0, 0, 0});
-      else if (c.kind == VK_STRING)
-        pb.code.push_back(Ins{OP_TRUTHY_S, (uint8_t)r, (uint8_t)r, 0, 0, string_code(E.snap.strings, "")});
-      plan.where_len = (int)pb.code.size();
-      plan.where_reg = r;
-    }
-    pb.next_reg = 0;   // WHERE registers are dead once its value is read
-  }
+  if (where)
+    if (int32_t rc = compile_where(E, *where, cenv, pb, &plan, &where_false)) return rc;
   std::unique_ptr<nbg_rows> res(new_rows(E, ny));
   res->derived = in->derived;
   ColTypeEnv tenv;
@@ -836,6 +873,297 @@ int32_t nbg_yield(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq
   uint64_t n = 0;
   if (int32_t rc = ws_yield_rows(d.w, E.stream, d.segs, plan, &ow, &n, &E.yr_prof, &err)) return E.fail(rc, err);
   if (ow) adopt_rows(res.get(), ow, n, ny);
+  *out = res.release();
+  return NBG_OK;
+}
+
+// ============================================================================= YIELD with aggregates
+// YieldExecutor::executeInputs with checkAggFun's functions and no GROUP BY
+// (src/graph/YieldExecutor.cpp:33-58, :178-282; AggregateFunction.h) over a device-resident result;
+// the kernels are in yieldagg.hip and, beside the interpreter, kernels.hip.
+namespace {
+
+struct YaValue {          // a function's argument: a register, an input column as it is, or a constant
+  int src = -1;           // YaSlot::src
+  int col = -1;           // the input column of a bare `$-.col'
+  VKind kind = VK_INT;
+  int32_t type = NBG_T_INT;   // Collector::getSchema: the kind's own type, or a root cast's
+  int64_t bits = 0;
+  std::string text;       // a constant string
+  bool is_const = false;
+  bool fails = false;     // a constant expression that fails to evaluate (OP_ERR on every row)
+};
+
+}  // namespace
+
+int32_t nbg_yield_agg(nbg_engine* h, const nbg_rows* in, const nbg_yield_request* rq, nbg_rows** out) {
+  if (!h || !in || !rq || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  // ---- 1. to 6.
+  YieldFront F;
+  if (int32_t rc = yield_front(E, in, rq, true, &F, out)) return rc;
+  if (F.done) return NBG_OK;
+  const int nc = in->ncols, ny = (int)F.yields.size();
+  const std::vector<std::string>& names = F.names;
+  std::string err;
+  // ---- 7. device scope
+  if (in->misaligned || in->float_col)
+    return E.fail(NBG_E_UNSUPPORTED, "YIELD: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (ny > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "YIELD: more than NBG_MAX_YIELDS columns");
+  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: the rows have no columns");
+  if (in->count > 0xFFFFFFFFull) return E.fail(NBG_E_UNSUPPORTED, "YIELD: an input of 2^32 rows or more");
+  const InputCols cols(in);
+  const std::vector<VKind>& kinds = cols.kind;
+  auto bare = [](const Node& n) { return n.kind == EK_INPUT || n.kind == EK_VAR; };
+  // a use: every function reads a bare column's cells as they are; what a string column may then
+  // feed is each function's own check below
+  auto check_use = [&](int c, bool is_bare) -> int32_t {
+    if (cols.mixed[c]) return E.fail(NBG_E_UNSUPPORTED, "YIELD: column `" + names[c] + "' mixes value kinds");
+    if (kinds[c] == VK_STRING && !is_bare && cols.outside[c])
+      return E.fail(NBG_E_UNSUPPORTED, "YIELD: column `" + names[c] + "' can hold strings outside the dictionary");
+    return NBG_OK;
+  };
+  {
+    YrRefs wr;
+    if (F.where) yr_refs(*F.where, &wr);
+    for (const std::string& p : wr.props)
+      if (int32_t rc = check_use(F.find_col(p), false)) return rc;
+    for (int y = 0; y < ny; ++y) {
+      YrRefs yr;
+      yr_refs(*F.yields[y], &yr);
+      for (const std::string& p : yr.props)
+        if (int32_t rc = check_use(F.find_col(p), bare(*F.yields[y]))) return rc;
+    }
+  }
+  // ---- compile: the WHERE, then one register per distinct argument expression
+  CompileEnv cenv = stage_env(E, true);
+  cenv.input_names = &names;
+  cenv.input_kinds = &kinds;
+  ColTypeEnv tenv;
+  tenv.input_names = &names;
+  tenv.input_kinds = &kinds;
+  ProgramBuilder pb;
+  YaPlan plan;
+  plan.nout = ny;
+  if (F.where)
+    if (int32_t rc = compile_where(E, *F.where, cenv, pb, &plan.y, &plan.none)) return rc;
+  // an argument's identity: its wire bytes (a column `$-.*' expanded to: the column)
+  auto encode = [](const Node& n, auto&& self, std::string* k) -> void {
+    k->push_back((char)n.kind);
+    k->push_back((char)n.op);
+    k->append(n.alias).push_back('\0');
+    k->append(n.prop).push_back('\0');
+    k->push_back((char)n.prim.index());
+    switch (n.prim.index()) {
+      case 0: k->append((const char*)&std::get<0>(n.prim), 8); break;
+      case 1: k->append((const char*)&std::get<1>(n.prim), 8); break;
+      case 2: k->push_back(std::get<2>(n.prim)); break;
+      default: k->append(std::get<3>(n.prim)).push_back('\0');
+    }
+    k->push_back((char)n.kids.size());
+    for (auto& kid : n.kids)
+      if (kid) self(*kid, self, k);
+  };
+  std::map<std::string, YaValue> args;
+  std::map<std::pair<std::string, int>, int> slots;   // (argument, YaOp) -> slot
+  std::set<int32_t> direct;                            // input columns read without the interpreter
+  auto argument = [&](const Node& n, std::string* key, YaValue* v) -> int32_t {
+    if (bare(n)) *key = "\x01" + std::to_string(F.find_col(n.prop));
+    else encode(n, encode, key);
+    auto it = args.find(*key);
+    if (it != args.end()) {
+      *v = it->second;
+      return NBG_OK;
+    }
+    if (bare(n)) {
+      v->col = F.find_col(n.prop);
+      v->src = -2 - v->col;
+      v->kind = kinds[v->col];
+      v->type = natural_type_of(v->kind);
+    } else {
+      Compiled c;
+      if (int32_t rc = compile_expr(n, cenv, pb, &c, &err, true)) return E.fail(rc, "YIELD: " + err);
+      v->is_const = c.is_const;
+      v->fails = c.always_error;
+      v->src = c.is_const ? -1 : c.reg;
+      v->kind = c.kind;
+      v->bits = c.is_const ? c.const_bits : 0;
+      if (c.is_const && c.kind == VK_STRING) v->text = c.const_str;
+      v->type = n.kind == EK_CAST ? yield_column_type(n, tenv) : 0;
+      if (!v->type) v->type = natural_type_of(c.kind);
+    }
+    args.emplace(*key, *v);
+    return NBG_OK;
+  };
+  auto slot = [&](const std::string& key, YaOp op, const YaValue& v, int ref) {
+    auto ins = slots.emplace(std::make_pair(key, (int)op), plan.nslots);
+    if (!ins.second) return ins.first->second;
+    plan.slot[plan.nslots] = YaSlot{(uint8_t)op, (uint8_t)(v.kind == VK_DOUBLE), (uint8_t)ref, v.src, v.bits};
+    if (v.col >= 0) direct.insert(v.col);
+    return plan.nslots++;
+  };
+  std::unique_ptr<nbg_rows> res(new_rows(E, ny));
+  res->derived = in->derived;
+  std::vector<uint8_t> is_avg(ny, 0);
+  bool needs_rows = false;   // a MAX, a MIN or a function-less column: status 9 when no row is kept
+  const double zero = 0.0;
+  int64_t zero_bits;
+  memcpy(&zero_bits, &zero, 8);
+  for (int y = 0; y < ny; ++y) {
+    const Node& n = *F.yields[y];
+    const int32_t fun = F.funs[y];
+    std::string key;
+    YaValue v;
+    if (int32_t rc = argument(n, &key, &v)) return rc;
+    YaOut& o = plan.out[y];
+    VKind okind = VK_INT;
+    int32_t otype = NBG_T_INT;
+    auto emit_const = [&](VKind k, int32_t t, int64_t bits) {
+      o = YaOut{YE_CONST, 0, bits};
+      okind = k;
+      otype = t;
+    };
+    // a string the functions compare by its code: a bare column inside the dictionary, or a constant
+    auto string_by_code = [&](const char* what) -> int32_t {
+      if (v.kind != VK_STRING || v.is_const) return NBG_OK;
+      if (v.col < 0) return E.fail(NBG_E_UNSUPPORTED, std::string("YIELD: ") + what + " over a string expression");
+      if (cols.outside[v.col])
+        return E.fail(NBG_E_UNSUPPORTED, std::string("YIELD: ") + what + " over a string column that can hold strings outside the dictionary");
+      return NBG_OK;
+    };
+    const bool int_like = v.type == NBG_T_INT || v.type == NBG_T_VID || v.type == NBG_T_TIMESTAMP;
+    const bool is_dbl = v.type == NBG_T_DOUBLE;
+    switch (fun) {
+      case NBG_AGG_NONE:   // Group::apply keeps the last row's value: here a constant's
+        if (v.fails) {
+          emit_const(VK_INT, NBG_T_INT, 0);   // a constant that fails to evaluate: every kept row's error
+        } else if (!v.is_const) {
+          return E.fail(NBG_E_UNSUPPORTED, "YIELD: a column without a function that is not constant");
+        } else {
+          emit_const(v.kind, v.type, v.bits);
+          if (v.kind == VK_STRING && (v.bits & 1)) res->const_str[0][y] = v.text;
+        }
+        needs_rows = true;
+        break;
+      case NBG_AGG_COUNT:
+        o = YaOut{YE_COUNT, 0, 0};
+        break;
+      case NBG_AGG_COUNT_DISTINCT: {
+        if (v.is_const) { emit_const(VK_INT, NBG_T_INT, 1); break; }
+        if (int32_t rc = string_by_code("COUNT_DISTINCT")) return rc;
+        emit_const(VK_INT, NBG_T_INT, 0);   // (the driver stores the count)
+        YaDistinct d;
+        d.out = y;
+        d.dbl = v.kind == VK_DOUBLE;
+        d.y.ncols = 1;
+        ProgramBuilder dpb;
+        bool unused = false;
+        if (F.where && !plan.none)
+          if (int32_t rc = compile_where(E, *F.where, cenv, dpb, &d.y, &unused)) return rc;
+        if (v.col >= 0) {
+          d.y.yield_reg[0] = -2 - v.col;
+        } else {
+          Compiled c;
+          if (int32_t rc = compile_expr(n, cenv, dpb, &c, &err, true)) return E.fail(rc, "YIELD: " + err);
+          d.y.yield_reg[0] = c.reg;
+        }
+        if (int32_t rc = finish_program(E, "YIELD", dpb, &d.y)) return rc;
+        plan.distinct.push_back(std::move(d));
+        break;
+      }
+      case NBG_AGG_SUM:
+        if (int_like) {
+          o = YaOut{YE_SLOT, (uint8_t)slot(key, YA_SUM_I, v, 0), 0};
+          otype = v.type;
+        } else if (is_dbl) {
+          o = YaOut{YE_SLOT, (uint8_t)slot(key, YA_SUM_D, v, 0), 0};
+          okind = VK_DOUBLE;
+          otype = NBG_T_DOUBLE;
+        }
+        break;
+      case NBG_AGG_AVG:
+        okind = VK_DOUBLE;
+        otype = NBG_T_DOUBLE;
+        is_avg[y] = 1;
+        if (v.type == NBG_T_TIMESTAMP) return E.fail(NBG_E_UNSUPPORTED, "YIELD: AVG over a TIMESTAMP-typed argument");
+        if (int_like) o = YaOut{YE_AVG_I, (uint8_t)slot(key, YA_SUM_I, v, 0), 0};
+        else if (is_dbl) o = YaOut{YE_AVG_D, (uint8_t)slot(key, YA_SUM_D, v, 0), 0};
+        else o = YaOut{YE_AVG_0, 0, 0};
+        break;
+      case NBG_AGG_MAX: case NBG_AGG_MIN: {
+        needs_rows = true;
+        if (v.is_const) {
+          emit_const(v.kind, v.type, v.bits);
+          if (v.kind == VK_STRING && (v.bits & 1)) res->const_str[0][y] = v.text;
+          break;
+        }
+        if (int32_t rc = string_by_code("MAX/MIN")) return rc;
+        okind = v.kind;
+        otype = v.type;
+        const YaOp op = fun == NBG_AGG_MAX ? YA_MAX : YA_MIN;
+        o = YaOut{(uint8_t)(v.kind == VK_DOUBLE ? YE_ORD_D : YE_ORD_I), (uint8_t)slot(key, op, v, 0), 0};
+        break;
+      }
+      case NBG_AGG_STD:
+        if (v.type == NBG_T_INT || is_dbl) {
+          const int s = slot(key, is_dbl ? YA_SUM_D : YA_SUM_I, v, 0);
+          o = YaOut{YE_STD, (uint8_t)slot(key, YA_SQ, v, s), 0};
+          okind = VK_DOUBLE;
+          otype = NBG_T_DOUBLE;
+          plan.has_sq = true;
+        }
+        break;
+      default: {   // BIT_AND / BIT_OR / BIT_XOR: INT-typed values only
+        if (v.type != NBG_T_INT) break;
+        const YaOp op = fun == NBG_AGG_BIT_AND ? YA_AND : fun == NBG_AGG_BIT_OR ? YA_OR : YA_XOR;
+        o = YaOut{YE_SLOT, (uint8_t)slot(key, op, v, 0), 0};
+      }
+    }
+    res->kinds[0][y] = okind;
+    res->col_types[y] = otype;
+  }
+  if (int32_t rc = finish_program(E, "YIELD", pb, &plan.y)) return rc;
+  if (plan.y.nregs + plan.nslots > interp_max_regs())
+    return E.fail(NBG_E_UNSUPPORTED, "YIELD: " + std::to_string(plan.y.nregs) + " registers and " + std::to_string(plan.nslots) +
+                                         " accumulators are over the register limit (" + std::to_string(interp_max_regs()) +
+                                         " fit the LDS)");
+  {
+    std::set<int32_t> wc, ac = direct;
+    for (int pc = 0; pc < (int)plan.y.code.size(); ++pc)
+      if (plan.y.code[pc].op == OP_COL) (pc < plan.y.where_len ? wc : ac).insert(plan.y.code[pc].aux);
+    plan.y.where_cols = (int)wc.size();
+    plan.arg_cols = (int)ac.size();
+  }
+  // ---- 8. the passes
+  DeviceInput d;
+  if (int32_t rc = device_input(E, "YIELD", in, &d)) return rc;
+  plan.y.str = E.dev_strings();
+  plan.y.now_sec = (int64_t)time(nullptr);
+  plan.y.rand_seed = query_rand_seed();
+  for (YaDistinct& cd : plan.distinct) {
+    cd.y.where_cols = plan.y.where_cols;
+    cd.y.yield_cols = 1;
+    cd.y.str = plan.y.str;
+    cd.y.now_sec = plan.y.now_sec;
+    cd.y.rand_seed = plan.y.rand_seed;
+  }
+  Workspace* ow = nullptr;
+  uint64_t kept = 0;
+  if (int32_t rc = ws_yield_agg(d.w, E.stream, d.segs, plan, &ow, &kept, &E.ya_prof, &E.yr_prof, &E.so_prof, &err)) return E.fail(rc, err);
+  RowsWs row;
+  row.w = ow;
+  // ---- 9. no row kept: a fresh function object's getResult; MAX, MIN and Group::apply hold an
+  // empty ColumnValue, which InterimResult::getResultWriter refuses (InterimResult.cpp:602-640)
+  if (!kept) {
+    if (needs_rows) return E.fail(NBG_E_EXECUTION_ERROR, "Not Support: 0");
+    for (int y = 0; y < ny; ++y) {
+      res->kinds[0][y] = is_avg[y] ? VK_DOUBLE : VK_INT;
+      res->col_types[y] = is_avg[y] ? NBG_T_DOUBLE : NBG_T_INT;
+    }
+  }
+  adopt_rows(res.get(), row.release(), 1, ny);
   *out = res.release();
   return NBG_OK;
 }

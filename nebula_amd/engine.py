@@ -441,7 +441,24 @@ class Engine:
         names ``rows``' columns, ``yields`` holds Expression::encode bytes per YIELD column (``$-.*``
         expands to every input column), ``where`` those of the WHERE (empty: none) and ``funs`` is
         None or one NBG_AGG_* value or name per column.  The result is a new DeviceRows in the
-        input's row order, filtered; ``rows`` stays valid and unchanged."""
+        input's row order, filtered; ``rows`` stays valid and unchanged.
+
+        Which call a YIELD sentence takes: one that references no ``$-`` / ``$var`` column is the
+        reference's executeConstant, which the caller answers itself; one with at least one
+        function is ``yield_agg``; every other one is this call (it answers a function with
+        NBG_E_UNSUPPORTED)."""
+        return self._yield_call("nbg_yield", "yield_rows", rows, input_names, yields, where, funs)
+
+    def yield_agg(self, rows: DeviceRows, input_names, yields, funs, where=b"") -> DeviceRows:
+        """nbg_yield_agg: ``| YIELD AVG($-.a), SUM($-.b * 2), COUNT(*), 1+1 WHERE where`` over a
+        device-resident result: a YIELD with at least one aggregate function and no GROUP BY.
+        ``yields`` holds Expression::encode bytes per column (a function's argument; ``COUNT(*)``: the
+        string primary ``"*"``), ``funs`` one NBG_AGG_* value or name per column (``""`` / 0: none,
+        for a constant column).  The result is a new DeviceRows of one row (none for an input without
+        rows); ``rows`` stays valid and unchanged."""
+        return self._yield_call("nbg_yield_agg", "yield_agg", rows, input_names, yields, where, funs)
+
+    def _yield_call(self, symbol, what, rows, input_names, yields, where, funs) -> DeviceRows:
         names = (C.c_char_p * max(1, len(input_names)))(*[n.encode() for n in input_names])
         bufs = [np.frombuffer(bytes(b), np.uint8).copy() for b in yields]
         ptrs = (C.POINTER(C.c_uint8) * max(1, len(bufs)))(*[b.ctypes.data_as(C.POINTER(C.c_uint8)) for b in bufs])
@@ -454,7 +471,7 @@ class Engine:
                                                      for f in funs])
         req = L.nbg_yield_request(names, wptr, len(wbuf), ptrs, lens, fptr, len(bufs))
         out = C.c_void_p()
-        self._check(self.lib.nbg_yield(self.h, rows.h, C.byref(req), C.byref(out)), "yield_rows")
+        self._check(getattr(self.lib, symbol)(self.h, rows.h, C.byref(req), C.byref(out)), what)
         return DeviceRows(self, out)
 
     def fetch_vertices(self, rows_or_vids, input_names, vid_col, tag_id, yields=(), distinct=False) -> DeviceRows:
