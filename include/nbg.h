@@ -15,6 +15,8 @@
  *       (src/storage/AddEdgesProcessor.cpp:15-37, src/kvstore/NebulaStore.cpp:326-336)
  *   nbg_go / nbg_go_device     ≙ GoExecutor result semantics (src/graph/GoExecutor.cpp:83-984)
  *   nbg_go_prepare / _execute  ≙ GoExecutor::prepare() / execute() (GoExecutor.cpp:28-110)
+ *   nbg_go_piped               ≙ GoExecutor::setupStarts over piped rows (GoExecutor.cpp:365-399,
+ *                                InterimResult::getVIDs / buildIndex, src/graph/InterimResult.cpp:29-250)
  *   nbg_find_path              ≙ FindPathExecutor result semantics
  *       (src/graph/FindPathExecutor.cpp:145-715)
  *   nbg_group_by               ≙ GroupByExecutor (src/graph/GroupByExecutor.cpp:181-322,
@@ -149,6 +151,18 @@ extern "C" {
  *   more than NBG_MAX_YIELDS columns; a program over 256 instructions or over the interpreter's
  *   register limit; an input of 2^32 rows or more; an edge type without a device CSR (registered,
  *   but no edge of it was loaded).
+ * nbg_go_piped (tests/test_gpu_go_piped.py holds one test per limit a GO result can reach; the
+ * mixed-kind columns and the row count are guards no test reaches):
+ *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
+ *   an input whose row schema re-reads its columns (a misaligned or FLOAT column);
+ *   a FROM column, or a column referenced by WHERE / YIELD, whose value kind differs between OVER
+ *   types (col_kind == -1);
+ *   a referenced string column that can hold strings outside the dictionary (a non-empty derived
+ *   table, or a per-OVER-type constant outside the dictionary): the host route gives such strings a
+ *   table of their own, which the device index does not build;
+ *   an input of 2^32 rows or more.
+ *   nbg_go's own limits stay, among them the 2^32 - 1 bound on the start list's entries plus edges,
+ *   which a piped list with duplicated hubs reaches easily (YIELD DISTINCT de-duplicates the list).
  * (A storage filter with a function call is E_INVALID_FILTER per part, as checkExp answers it,
  * QueryBaseProcessor.inl:172-290.)
  * Not limits: $- / $var input strings absent from the snapshot's dictionary, string functions
@@ -315,6 +329,49 @@ int32_t nbg_go(nbg_engine* e, const nbg_go_request* req, nbg_rows** out);
  * the live result (released by nbg_rows_free) and continues on a fresh one.  Every result must
  * be freed before nbg_destroy. */
 int32_t nbg_go_device(nbg_engine* e, const nbg_go_request* req, nbg_rows** out);
+
+/* ---- GO FROM $-.col / $var.col over a device-resident result (GoExecutor::setupStarts) ---------
+ * `... | GO [N STEPS] FROM $-.col OVER ... [WHERE ...] [YIELD [DISTINCT] ...]' whose left side is a
+ * result left in HBM by nbg_go_device, nbg_go_piped itself or any stage below: the start list and
+ * the $- / $var input index are built on the device from the rows where they lie and handed to the
+ * hop kernels of nbg_go (DESIGN.md "GO over device rows"); the host reads back one record of
+ * counters.  `in` must be a device-resident result of this engine; it stays valid and unchanged.
+ *
+ * req is nbg_go's request.  Of its input fields, input_names names `in`'s columns, num_input_cols
+ * must equal nbg_rows_num_cols(in) and input_vid_col is the FROM column; starts, num_starts,
+ * input_kinds, input_cols and num_input_rows are ignored (the kinds are `in`'s own).  device != 0
+ * leaves the rows in HBM as nbg_go_device does; otherwise they are copied to the host as by nbg_go.
+ * The result is an ordinary nbg_rows: every accessor works on it and a device result feeds every
+ * stage.
+ *
+ * For the same `in`, the rows (as a multiset), nbg_rows_step_stats, nbg_rows_edges_scanned and the
+ * status are those of nbg_go / nbg_go_device with `starts' set to the fetched FROM column and
+ * input_cols set to the fetched table, but for the device limits below:
+ *   starts keep duplicates; a vid that is no vertex of the snapshot contributes nothing;
+ *   under YIELD DISTINCT the starts are de-duplicated too (GoExecutor.cpp:101-107);
+ *   the input index keeps the last row per vid, "last" by `in`'s fetch order (segment order;
+ *   InterimResult.cpp:158-250);
+ *   a final row reads the input row of its source's root; a root without one is an evaluation error.
+ *
+ * Statuses, in this order:
+ *  1. NBG_E_INVALID_ARGUMENT: a null argument; `in` host-only or of another engine; input_names
+ *     null (or one of its entries); num_input_cols != nbg_rows_num_cols(in); input_vid_col out of
+ *     range; expression bytes that do not decode.
+ *  2. NBG_E_UNSUPPORTED: a partitioned engine.
+ *  3. Everything nbg_go_prepare answers for the statement, in its order, for an empty input too
+ *     (prepare() runs before setupStarts).
+ *  4. Zero input rows: NBG_OK and a zero-row result with the statement's columns (setupStarts
+ *     returns before getVIDs, :371-375; then onEmptyInputs).
+ *  5. NBG_E_EXECUTION_ERROR: the FROM column's kind is not INT, or its col_type is neither INT nor
+ *     VID ("Column `x' not found": RowReader::getVid, RowReader.cpp:569-576, as nbg_fetch_vertices
+ *     status 6).
+ *  6. Device scope: see "Device limits" (NBG_E_UNSUPPORTED; the caller then fetches `in` and calls
+ *     nbg_go with host inputs).
+ *  7. From here on as nbg_go: its limits (the start list's entries plus edges under 2^32 - 1 among
+ *     them), deferred name-resolution errors, evaluation errors, "Unknown Vertex".
+ * A start list of at most 32 found entries is read back and takes nbg_go's short-list path.  Single
+ * engine only; there is no prepared or asynchronous form. */
+int32_t nbg_go_piped(nbg_engine* e, const nbg_rows* in, const nbg_go_request* req, int32_t device, nbg_rows** out);
 
 /* Default YIELD of a GO without YIELD: the edge types whose `<edge>._dst` columns it returns, in
  * column order.  OVER e1, e2: the OVER order (parser.yy:518-531).  OVER * (over_all = 1, `over` =
@@ -1061,6 +1118,8 @@ typedef struct {
  * k_fe_resolve, k_fe_emit (DESIGN.md "FETCH PROP ON <edge> over device rows"). */
 /* ... and nbg_yield_agg's: k_ya_reduce, k_ya_finish (DESIGN.md "Aggregate YIELD over device rows");
  * its COUNT_DISTINCT columns are counted under nbg_yield's and nbg_set_op's kernels. */
+/* ... and nbg_go_piped's: k_gp_resolve, k_gp_table, k_gp_degrees, k_gp_emit, k_gp_compact (DESIGN.md
+ * "GO over device rows"); the hops after them are counted under nbg_go's kernels. */
 /* ---- FIND PATH replica of a partitioned engine (replica.hip) ---------------------------------
  * A partitioned engine (num_gpus > 1) also builds, at nbg_finalize (collectively), a replica of
  * every rank's path CSRs (offsets, neighbour ids and vids, ranks; no property columns) when it fits

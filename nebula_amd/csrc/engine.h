@@ -74,6 +74,7 @@ struct Engine {
   StageProf<YA_KINDS> ya_prof;                       // nbg_yield_agg's kernels
   StageProf<FV_KINDS> fv_prof;                       // nbg_fetch_vertices' kernels
   StageProf<FE_KINDS> fe_prof;                       // nbg_fetch_edges' kernels
+  StageProf<GP_KINDS> gp_prof;                       // nbg_go_piped's kernels
   // pinned host blocks of fetched GO rows (nbg_rows_fetch), reused across queries
   std::mutex pinned_mu;
   std::vector<std::pair<size_t, void*>> pinned_free;
@@ -178,6 +179,7 @@ void for_stage_profs(Eng& E, F f) {
   f(kFvKernelNames, E.fv_prof);   // nbg_fetch_vertices' (fetchrows.hip)
   f(kFeKernelNames, E.fe_prof);   // nbg_fetch_edges' (fetchedges.hip)
   f(kYaKernelNames, E.ya_prof);   // nbg_yield_agg's (yieldagg.hip)
+  f(kGpKernelNames, E.gp_prof);   // nbg_go_piped's (gopipe.hip)
 }
 
 int32_t engine_ready(Engine& E);   // workspace (+ partition buffers) after finalize / snapshot load

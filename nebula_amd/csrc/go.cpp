@@ -1,4 +1,5 @@
-// The GO N STEPS driver: prepared statements, the synchronous and the asynchronous entry points.
+// The GO N STEPS driver: prepared statements, the synchronous and the asynchronous entry points, and
+// GO FROM $-.col over a device-resident result (nbg_go_piped; its kernels are in gopipe.hip).
 //
 // GO N STEPS follows GoExecutor (src/graph/GoExecutor.cpp):
 //   * starts keep duplicates (prepareFrom :136-195); unknown vids contribute nothing;
@@ -47,6 +48,7 @@ struct nbg_go_stmt {
   bool uses_input = false;
   std::vector<int64_t> in_ids;
   std::vector<std::vector<int64_t>> in_cols;
+  uint64_t in_n = 0;                 // index rows (in_ids.size(), or what gopipe_index built on the device)
   int64_t* d_in_ids = nullptr;
   int64_t** d_in_cols = nullptr;
   std::vector<int64_t*> d_in_col_ptrs;
@@ -184,12 +186,22 @@ static int32_t prepare_clauses(Engine& E, const nbg_go_request* rq, const std::v
   return NBG_OK;
 }
 
-// $- / $var input: the index GoExecutor::setupStarts builds on the FROM column
-static int32_t prepare_input(Engine& E, const nbg_go_request* rq, nbg_go_stmt* st, GoClauses* cl) {
+// $- / $var input: the index GoExecutor::setupStarts builds on the FROM column.  `piped` (nbg_go_piped):
+// the input is a device-resident result; its columns' kinds are its own and the index is built on the
+// device once the statement is prepared (gopipe_index), so only the names and kinds are taken here.
+static int32_t prepare_input(Engine& E, const nbg_go_request* rq, nbg_go_stmt* st, GoClauses* cl, const nbg_rows* piped) {
   if (!st->uses_input) return NBG_OK;
   if (rq->num_input_cols <= 0) return E.fail(NBG_E_EXECUTION_ERROR, "$- / $var props need the piped or variable input");
   if (rq->num_input_cols > MAX_INPUT_COLS)
     return E.fail(NBG_E_UNSUPPORTED, "more than " + std::to_string(MAX_INPUT_COLS) + " input columns");
+  if (piped) {
+    for (int32_t c = 0; c < rq->num_input_cols; ++c) {
+      const int k = piped->col_kind(c);
+      cl->in_names.emplace_back(rq->input_names[c] ? rq->input_names[c] : "");
+      cl->in_kinds.push_back(k < 0 ? VK_INT : (VKind)k);
+    }
+    return NBG_OK;
+  }
   if (!rq->input_names || !rq->input_kinds || !rq->input_cols ||
       rq->input_vid_col < 0 || rq->input_vid_col >= rq->num_input_cols)
     return E.fail(NBG_E_INVALID_ARGUMENT, "input table");
@@ -208,6 +220,7 @@ static int32_t prepare_input(Engine& E, const nbg_go_request* rq, nbg_go_stmt* s
   }
   st->in_cols.assign(rq->num_input_cols, std::vector<int64_t>(rowof.size()));
   for (auto& pr : rowof) st->in_ids.push_back(pr.first);
+  st->in_n = st->in_ids.size();
   // strings the dictionary lacks (a string derived by an earlier statement of the pipe): a table of
   // their own, so they keep their bytes (a dictionary code between neighbours would not)
   std::vector<std::string>& in_xstr = st->in_xstr;   // (sorted, unique)
@@ -438,7 +451,7 @@ static void prepare_derived(nbg_go_stmt* st, GoClauses* cl) {
     }
 }
 
-static int32_t go_prepare(Engine& E, const nbg_go_request* rq, nbg_go_stmt** out) {
+static int32_t go_prepare(Engine& E, const nbg_go_request* rq, nbg_go_stmt** out, const nbg_rows* piped = nullptr) {
   if (!rq || !out) return E.fail(NBG_E_INVALID_ARGUMENT, "null argument");
   *out = nullptr;
   if (!E.finalized) return E.fail(NBG_E_STATE, "engine not finalized");
@@ -453,7 +466,7 @@ static int32_t go_prepare(Engine& E, const nbg_go_request* rq, nbg_go_stmt** out
   st->ncols = (int)cl.yields.size();
   st->uses_input = has_input_prop(cl.where.get());
   for (auto& y : cl.yields) st->uses_input = st->uses_input || has_input_prop(y.get());
-  if (int32_t rc = prepare_input(E, rq, st.get(), &cl)) return rc;
+  if (int32_t rc = prepare_input(E, rq, st.get(), &cl, piped)) return rc;
   // compile per OVER type
   alias_props(cl.where.get(), cl.named);
   for (auto& y : cl.yields) alias_props(y.get(), cl.named);
@@ -502,7 +515,9 @@ struct GoStarts {
     uint64_t all = 0, visible = 0;
     InlineList il{};   // filled when the list is short (inline_list())
   };
-  std::vector<uint32_t> f0;
+  std::vector<uint32_t> f0;     // (empty when the list is built on the device: `pipe`)
+  uint64_t n = 0;               // the list's entries
+  GoPipe* pipe = nullptr;       // nbg_go_piped: gopipe_list writes the list into the workspace
   std::vector<PerType> types;   // OVER order
   uint64_t start_edges = 0;     // the largest `all`
 
@@ -513,10 +528,34 @@ struct GoStarts {
       uint32_t d = E.dense(starts[i]);
       if (d != NO_ROW) f0.push_back(d);
     }
+    from_dense(E, st, cap);
+  }
+  // a short piped list, read back as dense ids in fetch order (nbg_go_piped)
+  GoStarts(const Engine& E, const nbg_go_stmt& st, std::vector<uint32_t> dense, uint32_t cap) : f0(std::move(dense)) {
+    from_dense(E, st, cap);
+  }
+  // a piped list that stays on the device: `count` entries (already unique under DISTINCT) whose
+  // capped degrees over OVER position i sum to all[i] (GpCounts::deg of the types that have a CSR)
+  GoStarts(const nbg_go_stmt& st, GoPipe* p, uint64_t count, const std::vector<uint64_t>& all) : n(count), pipe(p) {
+    types.resize(st.over.size());
+    for (size_t i = 0; i < st.over.size(); ++i) {
+      types[i].all = all[i];
+      types[i].il.n_in = (uint32_t)n;
+      start_edges = std::max(start_edges, all[i]);
+    }
+  }
+  // a short start list travels to the first expansion in its kernel arguments, with its edge
+  // space over each OVER type computed here from the host CSR offsets (no k_relist launch)
+  bool inline_list() const { return !pipe && n <= (uint64_t)INLINE_STARTS; }
+  const InlineList* inline_of(size_t i, uint32_t step) const { return step == 1 && inline_list() ? &types[i].il : nullptr; }
+
+ private:
+  void from_dense(const Engine& E, const nbg_go_stmt& st, uint32_t cap) {
     if (st.distinct) {   // DISTINCT de-duplicates the starts too (GoExecutor.cpp:101-107)
       std::sort(f0.begin(), f0.end());
       f0.erase(std::unique(f0.begin(), f0.end()), f0.end());
     }
+    n = f0.size();
     types.resize(st.over.size());
     const std::vector<uint8_t>& vis = E.snap.h_visible;
     for (size_t i = 0; i < st.over.size(); ++i) {
@@ -542,10 +581,6 @@ struct GoStarts {
       start_edges = std::max(start_edges, pt.all);
     }
   }
-  // a short start list travels to the first expansion in its kernel arguments, with its edge
-  // space over each OVER type computed here from the host CSR offsets (no k_relist launch)
-  bool inline_list() const { return f0.size() <= (size_t)INLINE_STARTS; }
-  const InlineList* inline_of(size_t i, uint32_t step) const { return step == 1 && inline_list() ? &types[i].il : nullptr; }
 };
 
 // What the phases of one go_launch share.
@@ -593,7 +628,7 @@ struct GoQuery {
     a.str = E.dev_strings();
     if (st->uses_input) {
       a.in_ids = st->d_in_ids;
-      a.in_n = st->in_ids.size();
+      a.in_n = st->in_n;
       a.in_cols = st->d_in_cols;
       a.str.xoff = st->d_xoff;
       a.str.xbytes = st->d_xbytes;
@@ -655,9 +690,9 @@ static void go_workspace(GoQuery& q, const GoStarts& S, uint64_t num_starts, Wor
   }
   // room for a duplicated start list: the decision comes from the whole start list, the same on
   // every rank of a partitioned engine (its own share, f0, is at most that)
-  const uint64_t need = q.part ? std::max<uint64_t>(num_starts, 1) : S.f0.size();
+  const uint64_t need = q.part ? std::max<uint64_t>(num_starts, 1) : S.n;
   const uint64_t e_need = std::max<uint64_t>(E.snap.max_edges(), S.start_edges);
-  if (!q.lrc && (!*wsp || need > ws_cap_frontier(*wsp) || S.f0.size() + S.start_edges > ws_cap_items(*wsp))) {
+  if (!q.lrc && (!*wsp || need > ws_cap_frontier(*wsp) || S.n + S.start_edges > ws_cap_items(*wsp))) {
     const uint64_t fcap = std::max<uint64_t>({need, E.snap.nv + 1024, ws_cap_frontier(*wsp ? *wsp : nullptr)});
     std::string err;
     Workspace* fresh = ws_fresh(E, fcap, e_need, q.stream, q.qcomm, *wsp, &err);
@@ -834,7 +869,7 @@ static hipError_t go_steps(GoQuery& q, const GoStarts& S, const RowPlan& plan, c
   const std::vector<TypeProgram>& plist = q.st->plist;
   const uint32_t steps = q.st->steps;
   Workspace* ws = q.ws;
-  uint64_t n_bound = S.f0.size();
+  uint64_t n_bound = S.n;
   ws_set_mark_claims(ws, over.size() == 1);
   const bool inject = q.part && E.fault(NBG_FAULT_DEVICE);
   for (uint32_t s = 1; he == hipSuccess && s <= steps; ++s) {
@@ -921,24 +956,22 @@ static hipError_t go_end(const GoQuery& q, const RowPlan& plan, bool device) {
 // the mapped flag.  A submitted query is waited for by its event: the other slots' queries hide
 // the wake-up, and the event lets the runtime retire finished work (six in flight ran ~1 %
 // slower on the flag, profiles/r04_w/x_go_wake_ab*.txt).
-static int32_t go_launch(Engine& E, nbg_go_stmt* st, const int64_t* starts, uint64_t num_starts, bool device,
-                         Workspace** wsp, hipStream_t stream, Comm* qcomm, GoPending* p, bool sync,
-                         int32_t pre_rc = NBG_OK, const char* pre_msg = nullptr) {
-  if (num_starts && !starts) return E.fail(NBG_E_INVALID_ARGUMENT, "null argument");
-  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+// S: the query's start list (nbg_go_piped builds it from device rows; `starts` is then unused).
+static int32_t go_launch_list(Engine& E, nbg_go_stmt* st, const GoStarts& S, const int64_t* starts, uint64_t num_starts,
+                              bool device, Workspace** wsp, hipStream_t stream, Comm* qcomm, GoPending* p, bool sync,
+                              int32_t pre_rc = NBG_OK, const char* pre_msg = nullptr) {
   const bool part = E.partitioned();
   if (part && !qcomm) return E.fail(NBG_E_STATE, "partitioned engine without a communicator");
   GoQuery q{E, st, stream, qcomm, part, E.edge_cap()};
   const std::vector<int32_t>& over = st->over;
   const uint32_t steps = st->steps;
-  const GoStarts S(E, *st, starts, num_starts, q.cap);
   std::unique_ptr<nbg_rows> rows(new nbg_rows());
   rows->eng = &E;
   rows->ncols = st->ncols;
   rows->on_device = device;
   p->device = device;
   // (partitioned: every rank runs the same collective sequence, even with no local start)
-  if (S.f0.empty() && !part) {
+  if (!S.n && !part) {
     p->finished = true;
     p->rows = std::move(rows);
     return NBG_OK;
@@ -948,7 +981,7 @@ static int32_t go_launch(Engine& E, nbg_go_stmt* st, const int64_t* starts, uint
   // The start list keeps duplicates, so its edge space is the one list not bounded by a type's
   // edge count: the device lists carry it in 32 bits, and the workspace's merge-path tile splits
   // must cover it (on a partitioned engine each rank checks its own share).
-  if (S.f0.size() + S.start_edges >= 0xFFFFFFFFull)   // merge-path items (entries + edges) are 32-bit too
+  if (S.n + S.start_edges >= 0xFFFFFFFFull)   // merge-path items (entries + edges) are 32-bit too
     q.local_fail(NBG_E_UNSUPPORTED, "the start list's edges exceed 2^32-1 (duplicated hub starts)");
   go_workspace(q, S, num_starts, wsp);
   Workspace* ws = q.ws;
@@ -968,7 +1001,7 @@ static int32_t go_launch(Engine& E, nbg_go_stmt* st, const int64_t* starts, uint
     auto it = E.snap.types.find(over[i]);
     if (it != E.snap.types.end()) ebound[i] = steps == 1 ? S.types[i].all : it->second.num_edges;
   }
-  RowPlan plan = row_regions(steps == 1 ? S.f0.size() : E.snap.nv, ebound);
+  RowPlan plan = row_regions(steps == 1 ? S.n : E.snap.nv, ebound);
   if (!q.lrc && ws_reserve_rows(ws, plan.cap_rows, st->ncols) != hipSuccess)
     q.local_fail(NBG_E_OUT_OF_MEMORY, "result rows");
   if (!q.lrc && st->derived && ws_reserve_arena(ws, arena_size(st, plan.cap_rows)) != hipSuccess)
@@ -978,7 +1011,10 @@ static int32_t go_launch(Engine& E, nbg_go_stmt* st, const int64_t* starts, uint
   p->ws = ws;
   rows->ws = ws;
   stmt_index_build(q);
-  hipError_t he = ws_begin_query(ws, S.f0.data(), S.f0.size(), &st->plist, st->id);
+  hipError_t he = S.pipe ? gopipe_list(S.pipe, ws, nullptr) : hipSuccess;
+  if (he == hipSuccess)
+    he = S.pipe ? ws_begin_query_resident(ws, S.n, &st->plist, st->id)
+                : ws_begin_query(ws, S.f0.data(), S.f0.size(), &st->plist, st->id);
   if (const DevEdgeType* tdt = he == hipSuccess ? tiny_type(q, S, device) : nullptr) {
     he = ws_go_tiny(ws, q.args_for(*tdt), S.f0.data(), (uint32_t)S.f0.size(), steps, st->plist[0], st->ncols);
     if (he != hipSuccess) return E.fail(NBG_E_DEVICE, std::string("HIP: ") + hipGetErrorString(he));
@@ -1000,6 +1036,15 @@ static int32_t go_launch(Engine& E, nbg_go_stmt* st, const int64_t* starts, uint
   p->blk_cap = std::move(plan.blk_cap);
   p->rows = std::move(rows);
   return NBG_OK;
+}
+
+static int32_t go_launch(Engine& E, nbg_go_stmt* st, const int64_t* starts, uint64_t num_starts, bool device,
+                         Workspace** wsp, hipStream_t stream, Comm* qcomm, GoPending* p, bool sync,
+                         int32_t pre_rc = NBG_OK, const char* pre_msg = nullptr) {
+  if (num_starts && !starts) return E.fail(NBG_E_INVALID_ARGUMENT, "null argument");
+  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+  const GoStarts S(E, *st, starts, num_starts, E.edge_cap());
+  return go_launch_list(E, st, S, starts, num_starts, device, wsp, stream, qcomm, p, sync, pre_rc, pre_msg);
 }
 
 // ----------------------------------------------------------------------------- go_collect's phases
@@ -1233,6 +1278,130 @@ static int32_t go_impl(Engine& E, const nbg_go_request* rq, bool device, nbg_row
   return go_execute(E, st, rq->starts, rq->num_starts, device, out);
 }
 
+// ----------------------------------------------------------------------------- GO over device rows
+// nbg_go_piped: GoExecutor::setupStarts (GoExecutor.cpp:365-399) over a device-resident result.  The
+// statement is prepared as nbg_go prepares it; the start list and the input index come from
+// gopipe.hip; everything after the start list is go_launch_list / go_collect.  The numbered steps
+// are the statuses of include/nbg.h, in their order.
+static int32_t go_piped(Engine& E, const nbg_rows* in, const nbg_go_request* rq, bool device, nbg_rows** out) {
+  // ---- 1. arguments
+  if (in->eng != &E) return E.fail(NBG_E_INVALID_ARGUMENT, "GO FROM $-: the rows belong to another engine");
+  if (!in->on_device) return E.fail(NBG_E_INVALID_ARGUMENT, "GO FROM $-: the rows are host-only (not a device result)");
+  if (!rq->input_names) return E.fail(NBG_E_INVALID_ARGUMENT, "GO FROM $-: null input column names");
+  if (rq->num_input_cols != in->ncols)
+    return E.fail(NBG_E_INVALID_ARGUMENT, "GO FROM $-: " + std::to_string(rq->num_input_cols) + " input column names for " +
+                                              std::to_string(in->ncols) + " columns");
+  for (int32_t c = 0; c < rq->num_input_cols; ++c)
+    if (!rq->input_names[c]) return E.fail(NBG_E_INVALID_ARGUMENT, "GO FROM $-: null input column name");
+  const int vcol = rq->input_vid_col;
+  if (vcol < 0 || vcol >= in->ncols) return E.fail(NBG_E_INVALID_ARGUMENT, "GO FROM $-: the FROM column is out of range");
+  if (rq->num_yields < 0 || (rq->num_yields > 0 && (!rq->yields || !rq->yield_lens)))
+    return E.fail(NBG_E_INVALID_ARGUMENT, "GO FROM $-: null argument");
+  {
+    std::string err;
+    if (rq->where && rq->where_len && !decode_expr(rq->where, rq->where_len, &err))
+      return E.fail(NBG_E_INVALID_ARGUMENT, "WHERE: " + err);
+    for (int32_t i = 0; i < rq->num_yields; ++i)
+      if (!decode_expr(rq->yields[i], rq->yield_lens[i], &err)) return E.fail(NBG_E_INVALID_ARGUMENT, "YIELD: " + err);
+  }
+  // ---- 2.
+  if (E.partitioned())
+    return E.fail(NBG_E_UNSUPPORTED, "GO FROM $- on a partitioned engine (its rows live on several ranks)");
+  // ---- 3. prepare() runs before setupStarts: diagnosed for an empty input too
+  nbg_go_stmt* stp = nullptr;
+  if (int32_t rc = go_prepare(E, rq, &stp, in)) return rc;
+  const std::unique_ptr<nbg_go_stmt> own(stp);
+  nbg_go_stmt* st = stp;
+  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+  const uint32_t cap = E.edge_cap();
+  GoPending p;
+  auto run = [&](const GoStarts& S) {
+    if (int32_t rc = go_launch_list(E, st, S, nullptr, 0, device, &E.ws, E.stream, E.comm.get(), &p, true)) return rc;
+    return go_collect(E, st, &p, out);
+  };
+  // ---- 4. no rows: setupStarts returns before getVIDs, then onEmptyInputs
+  if (!in->count) return run(GoStarts(E, *st, nullptr, 0, cap));
+  // ---- 5. getVIDs -> RowReader::getVid (RowReader.cpp:569-576): INT and VID columns only
+  const int vkind = in->col_kind(vcol);
+  const int32_t vtype = vcol < (int)in->col_types.size() && in->col_types[vcol] ? in->col_types[vcol]
+                        : vkind == VK_DOUBLE ? NBG_T_DOUBLE : vkind == VK_BOOL ? NBG_T_BOOL
+                        : vkind == VK_STRING ? NBG_T_STRING : NBG_T_INT;
+  if ((vkind >= 0 && vkind != VK_INT) || (vtype != NBG_T_INT && vtype != NBG_T_VID))
+    return E.fail(NBG_E_EXECUTION_ERROR, std::string("Column `") + rq->input_names[vcol] + "' not found");
+  // ---- 6. device scope
+  if (in->misaligned || in->float_col)
+    return E.fail(NBG_E_UNSUPPORTED, "GO FROM $-: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (vkind < 0) return E.fail(NBG_E_UNSUPPORTED, std::string("GO FROM $-: column `") + rq->input_names[vcol] + "' mixes value kinds");
+  uint32_t refs = 0;   // the input columns WHERE / YIELD read (OP_INPUT's aux)
+  for (const TypeProgram& tp : st->plist)
+    for (const Ins& i : tp.code)
+      if (i.op == OP_INPUT && i.aux >= 0 && i.aux < in->ncols) refs |= 1u << i.aux;
+  for (int c = 0; c < in->ncols; ++c) {
+    if (!((refs >> c) & 1u)) continue;
+    const int k = in->col_kind(c);
+    if (k < 0) return E.fail(NBG_E_UNSUPPORTED, std::string("GO FROM $-: column `") + rq->input_names[c] + "' mixes value kinds");
+    bool outside = !in->derived.empty();
+    for (auto& cs : in->const_str) outside = outside || ((int)cs.size() > c && !cs[c].empty());
+    if (k == VK_STRING && outside)
+      return E.fail(NBG_E_UNSUPPORTED, std::string("GO FROM $-: string column `") + rq->input_names[c] +
+                                           "' can hold strings outside the dictionary");
+  }
+  if (in->count > 0xFFFFFFFFull) return E.fail(NBG_E_UNSUPPORTED, "GO FROM $-: an input of 2^32 rows or more");
+  if (!E.snap.d_vids || in->ncols > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "GO FROM $-: vertex table missing");
+  // ---- 7. the join and the counts, one read-back
+  auto* m = const_cast<nbg_rows*>(in);
+  m->build_segs();
+  std::vector<std::pair<uint64_t, uint64_t>> segs;
+  for (auto& sg : m->segs)
+    if (sg.end > sg.begin) segs.emplace_back(sg.begin, sg.end - sg.begin);
+  Workspace* inw = in->owned_ws ? in->owned_ws : in->ws;
+  if (!inw) return E.fail(NBG_E_INVALID_ARGUMENT, "GO FROM $-: the rows have no device workspace");
+  GpPlan gp;
+  gp.vid_col = vcol;
+  gp.vids = E.snap.d_vids;
+  gp.nv = E.snap.nv;
+  gp.distinct = st->distinct;
+  gp.index = st->uses_input;
+  gp.cap = cap;
+  std::vector<int> slot(st->over.size(), -1);   // OVER position -> GpCounts::deg entry
+  for (size_t i = 0; i < st->over.size(); ++i) {
+    auto it = E.snap.types.find(st->over[i]);
+    if (it == E.snap.types.end() || !it->second.row_ptr) continue;
+    slot[i] = gp.ntypes;
+    gp.row_ptr[gp.ntypes++] = it->second.row_ptr;
+  }
+  GoPipe* pipe = nullptr;
+  GpCounts got{};
+  std::string err;
+  if (int32_t rc = gopipe_open(inw, E.stream, segs, gp, &E.gp_prof, &pipe, &got, &err)) return E.fail(rc, err);
+  const std::unique_ptr<GoPipe, void (*)(GoPipe*)> closer(pipe, gopipe_close);   // (after the query's last wait)
+  const uint64_t nlist = st->distinct ? got.unique : got.found;
+  if (!nlist) return run(GoStarts(E, *st, nullptr, 0, cap));
+  // the input index, owned by this one-shot statement (freed with it)
+  if (st->uses_input) {
+    const hipError_t he = gopipe_index(pipe, refs, in->ncols, &st->d_in_ids, &st->d_in_col_ptrs);
+    bool ok = he == hipSuccess;
+    ok = ok && hipMalloc((void**)&st->d_in_cols, std::max<size_t>(st->d_in_col_ptrs.size(), 1) * 8) == hipSuccess &&
+         hipMemcpyAsync(st->d_in_cols, st->d_in_col_ptrs.data(), st->d_in_col_ptrs.size() * 8, hipMemcpyHostToDevice,
+                        E.stream) == hipSuccess;
+    if (!ok) {
+      (void)hipGetLastError();
+      return E.fail(he == hipSuccess || he == hipErrorOutOfMemory ? NBG_E_OUT_OF_MEMORY : NBG_E_DEVICE, "GO FROM $-: input index");
+    }
+    st->in_n = got.unique;
+  }
+  // a short list is read back and takes the host start-list path (the inline list, the tiny path)
+  if (nlist <= (uint64_t)INLINE_STARTS) {
+    std::vector<uint32_t> dense(nlist);
+    if (gopipe_list(pipe, nullptr, dense.data()) != hipSuccess) return E.fail(NBG_E_DEVICE, "GO FROM $-: start list read");
+    return run(GoStarts(E, *st, std::move(dense), cap));
+  }
+  std::vector<uint64_t> all(st->over.size(), 0);
+  for (size_t i = 0; i < st->over.size(); ++i)
+    if (slot[i] >= 0) all[i] = got.deg[slot[i]];
+  return run(GoStarts(*st, pipe, nlist, all));
+}
+
 }  // namespace
 
 // ============================================================================= asynchronous GO
@@ -1373,6 +1542,13 @@ int32_t nbg_go(nbg_engine* h, const nbg_go_request* req, nbg_rows** out) {
 int32_t nbg_go_device(nbg_engine* h, const nbg_go_request* req, nbg_rows** out) {
   if (!h) return NBG_E_INVALID_ARGUMENT;
   return go_impl(h->e, req, true, out);
+}
+
+int32_t nbg_go_piped(nbg_engine* h, const nbg_rows* in, const nbg_go_request* req, int32_t device, nbg_rows** out) {
+  if (!h || !in || !req || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  std::lock_guard<std::mutex> lg(h->e.mu);
+  return go_piped(h->e, in, req, device != 0, out);
 }
 
 int32_t nbg_go_default_columns(nbg_engine* h, const int32_t* over, int32_t n, int32_t over_all, int32_t* out,

@@ -1270,15 +1270,7 @@ hipError_t launch_ya_reduce(const YaArgs& a, unsigned grid, hipStream_t s) {
 // CompileEnv's fetch mode: `tag.prop` is OP_TAGS_E with gbase = 0 and EdgeCtx::v = the row's dense
 // vertex id, which k_fv_resolve found.  Chunks and LDS registers as k_yr_*.
 
-// the vid -> dense id join: the first entry of vids[lo, hi) not below `vid` (signed order)
-__device__ __forceinline__ uint64_t fv_lower_bound(const int64_t* __restrict__ vids, uint64_t lo, uint64_t hi, int64_t vid) {
-  while (lo < hi) {
-    const uint64_t mid = (lo + hi) >> 1;
-    if (vids[mid] < vid) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
+// (the vid -> dense id join, fv_lower_bound, is in stage.h: gopipe.hip searches the same way)
 
 // per row: the vid cell, its dense id (4 bytes) and a keep byte (in d_vids, carries the tag, lives
 // in the part the storage client asks); per chunk the kept count (a plain store, as k_yr_filter).
@@ -2728,9 +2720,15 @@ hipError_t ws_wait(Workspace* w) {
   return e;
 }
 
+hipError_t ws_begin_query_resident(Workspace* w, uint64_t n, const std::vector<TypeProgram>* progs, uint64_t stmt_id) {
+  if (n <= INLINE_STARTS) return hipErrorInvalidValue;   // (a short list travels in the kernel arguments)
+  return ws_begin_query(w, nullptr, n, progs, stmt_id);
+}
+
+// starts == nullptr (ws_begin_query_resident): the list already lies in frontier[0]
 hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, const std::vector<TypeProgram>* progs,
                           uint64_t stmt_id) {
-  if (n > w->cap_frontier) return hipErrorInvalidValue;
+  if (n > w->cap_frontier || (!starts && n <= INLINE_STARTS && n)) return hipErrorInvalidValue;
   w->cur = 0;
   w->seg_ready = false;
   w->list_acc = nullptr;
@@ -2741,7 +2739,7 @@ hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, cons
   if (w->start_inline) {
     w->inl.n = (uint32_t)n;
     for (uint64_t i = 0; i < n; ++i) w->inl.id[i] = starts[i];
-  } else {
+  } else if (starts) {
     if (n > w->cap_starts) {
       if (w->h_starts) HIP_TRY(hipHostFree(w->h_starts));
       w->cap_starts = n + n / 2 + 1024;

@@ -1060,9 +1060,51 @@ int32_t ws_fetch_edges(Workspace* inw, const int64_t* host_src, const int64_t* h
                        hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs, const FePlan& plan,
                        Workspace** outw, uint64_t* rows, StageProf<FE_KINDS>* prof, std::string* err);
 
+// ---- GO FROM $-.col over device rows (gopipe.hip; GoExecutor::setupStarts, GoExecutor.cpp:365-399,
+// InterimResult::getVIDs / buildIndex).  The FROM column is joined to the dense vertex ids
+// (k_gp_resolve, which also keeps the last logical row of every vertex in a table of nv entries),
+// the found rows and the table's entries are counted and ranked (k_gp_table, k_yr_scan), the start
+// list's capped degrees are summed per OVER type (k_gp_degrees; under DISTINCT in k_gp_table), the
+// host reads GpCounts back once, and then the start list (k_gp_emit in fetch order, k_gp_compact
+// ascending and unique under DISTINCT) and the $- / $var input index (k_gp_compact) are written
+// where the hop kernels read them.
+enum GpKernel { GP_K_RESOLVE = 0, GP_K_TABLE, GP_K_DEGREES, GP_K_EMIT, GP_K_COMPACT, GP_KINDS };   // (k_yr_scan is untimed here)
+extern const char* const kGpKernelNames[GP_KINDS];
+struct GpPlan {
+  int vid_col = -1;                 // the FROM column
+  const int64_t* vids = nullptr;    // Snapshot::d_vids / nv
+  uint64_t nv = 0;
+  bool distinct = false;            // the start list is the table's entries (ascending, unique)
+  bool index = false;               // the statement reads $- / $var: the table feeds the input index
+  int ntypes = 0;                   // OVER types with a CSR on the device, and their row offsets
+  const uint32_t* row_ptr[MAX_TYPES_Q] = {};
+  uint32_t cap = 0;                 // max_edge_returned_per_vertex
+};
+// what the host reads back: `found` rows resolved, `unique` vertices among them (0 unless the table
+// was built), deg[i] = the start list's capped degrees over row_ptr[i]
+struct GpCounts {
+  unsigned long long found, found_err, unique, unique_err;   // (two YrState, as k_yr_scan writes them)
+  unsigned long long deg[MAX_TYPES_Q];
+};
+struct GoPipe;   // the scratch, chunks and timer of one call (gopipe.hip)
+// The join and the counts over the rows of `inw` listed by segs, on `stream`; waits once.  *out
+// lives until gopipe_close, which the caller runs after the query's last wait.
+int32_t gopipe_open(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
+                    const GpPlan& plan, StageProf<GP_KINDS>* prof, GoPipe** out, GpCounts* counts, std::string* err);
+// The start list (counts.unique entries under DISTINCT, else counts.found): into the start buffer of
+// `ws` when given, else into a scratch list that is copied to host[] (waits).  Enqueued on the stream.
+hipError_t gopipe_list(GoPipe* p, Workspace* ws, uint32_t* host);
+// The input index: in_ids[counts.unique] and, for every column of `mask`, cols[c][counts.unique],
+// allocated here (hipMalloc; the caller frees them), filled on the stream.
+hipError_t gopipe_index(GoPipe* p, uint32_t mask, int ncols, int64_t** in_ids, std::vector<int64_t*>* cols);
+void gopipe_close(GoPipe* p);
+
 // Query pipeline (all asynchronous on the workspace stream until ws_end_query):
 hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, const std::vector<TypeProgram>* progs,
                           uint64_t stmt_id);
+// ... from a start list of n > INLINE_STARTS dense ids that already lies in the workspace's start
+// buffer (gopipe_list wrote it there, on the workspace's stream)
+hipError_t ws_begin_query_resident(Workspace* w, uint64_t n, const std::vector<TypeProgram>* progs, uint64_t stmt_id);
 // steps 1..N-1, per OVER type: scan + expand into the next frontier.  Single engine: every new
 // neighbour is CLAIMED against a per-step stamp and appended to the next list (with its edge
 // space over next0 = the first OVER type's CSR of step + 1); partitioned: byte flags over the

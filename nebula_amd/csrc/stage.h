@@ -1,5 +1,5 @@
 // nebula_amd — the frame of a driver of a stage over device-resident rows (groupby.hip, orderby.hip,
-// setops.hip, yieldrows.hip, yieldagg.hip, fetchrows.hip, fetchedges.hip): the status of its HIP calls, its result workspace
+// setops.hip, yieldrows.hip, yieldagg.hip, fetchrows.hip, fetchedges.hip, gopipe.hip): the status of its HIP calls, its result workspace
 // (RowsWs, nbg_internal.h), the scratch of one call, the event pairs nbg_profile puts around each
 // launch, the chunk list that spreads an input's segments over the device, and the YrPlan setup
 // YIELD and FETCH share.  A driver declares its scratch before its timer: the timer's events are
@@ -20,6 +20,17 @@ constexpr unsigned STAGE_GRID = 2048;   // 8 workgroups per CU; the chunks beyon
 
 __device__ __forceinline__ uint32_t lane_rank(unsigned long long bal) {   // set bits below this lane
   return __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
+}
+
+// the vid -> dense id join (k_fv_resolve, k_fe_resolve, k_gp_resolve): the first entry of
+// vids[lo, hi) not below `vid` (signed order)
+__device__ __forceinline__ uint64_t fv_lower_bound(const int64_t* __restrict__ vids, uint64_t lo, uint64_t hi, int64_t vid) {
+  while (lo < hi) {
+    const uint64_t mid = (lo + hi) >> 1;
+    if (vids[mid] < vid) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
 }
 
 // what a driver's HIP calls came to: `failed` records and tests one, `code` reports the last

@@ -388,6 +388,32 @@ class Engine:
         self._check(rc, "go_device")
         return DeviceRows(self, out)
 
+    def go_piped(self, rows: DeviceRows, input_names, vid_col, etypes, steps=1, where=b"", yields=(), distinct=False,
+                 over_all=False, device=True):
+        """nbg_go_piped: ``| GO [N STEPS] FROM $-.vid_col OVER ... [WHERE ...] [YIELD [DISTINCT] ...]``
+        over a device-resident result.  ``input_names`` names ``rows``' columns and ``vid_col`` is
+        the FROM column's name; ``$-.x`` / ``$var.x`` in ``where`` / ``yields`` read the input row of
+        a final row's root, the last row of a vid winning.  The start list and that index are built
+        on the device from the rows where they lie.  Returns a new DeviceRows (``device=False``: host
+        rows, as ``go``); ``rows`` stays valid and unchanged."""
+        req, keep = self._go_request([], etypes, steps, where, yields, distinct, over_all)
+        names = list(input_names)
+        cname = (C.c_char_p * max(1, len(names)))(*[n.encode() for n in names])
+        req.num_input_cols, req.input_names = len(names), cname
+        req.input_vid_col = names.index(vid_col) if vid_col in names else -1
+        out = C.c_void_p()
+        self._check(self.lib.nbg_go_piped(self.h, rows.h, C.byref(req), int(bool(device)), C.byref(out)), "go_piped")
+        if device:
+            return DeviceRows(self, out)
+        try:
+            f = (C.c_uint64 * 16)()
+            e = (C.c_uint64 * 16)()
+            k = self.lib.nbg_rows_step_stats(out, f, e, 16)
+            self.last_step_stats = (list(f[:k]), list(e[:k]), self.lib.nbg_rows_edges_scanned(out))
+            return self._host_rows(out)
+        finally:
+            self.lib.nbg_rows_free(out)
+
     def group_by(self, rows: DeviceRows, input_names, groups, yields) -> DeviceRows:
         """nbg_group_by: ``| GROUP BY groups YIELD yields`` over a device-resident result.
         ``input_names`` names ``rows``' columns, ``groups`` holds Expression::encode bytes per group
