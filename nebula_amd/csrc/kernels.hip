@@ -3094,6 +3094,13 @@ static bool lean_final() {
   return on;
 }
 
+// NBG_FINAL_COPY=0 (read per call, as NBG_FINAL_GRID is): k_final_dst runs the indexed
+// single-_dst final step as well (A/B)
+static bool final_copy_on() {
+  const char* ev = getenv("NBG_FINAL_COPY");
+  return !ev || atoi(ev) != 0;
+}
+
 // The final step runs final.hip's kernel with a WHERE column to read: the shape a statement's
 // filtered adjacency replaces.
 static bool final_where_shape(const FastProg& f, const ExpandArgs& a) {
@@ -3204,7 +3211,26 @@ hipError_t ws_expand_final(Workspace* w, const ExpandArgs& a0, uint64_t n_bound,
     fa.stat_n = L.stat_n;
     fa.err_flag = &w->q->err;
     const bool one = fp.nyields == 1 && fa.const_mask == 0;
-    const hipError_t le = launch_final_dst(fa, fp.fast.has_where ? fp.fast.wbytes : 0, one, grid.x, w->stream);
+    hipError_t le;
+    if (full_row_ptr && one && final_copy_on()) {   // a segmented copy: every row's place is known (finalcopy.hip)
+      FinalCopyArgs ca{};
+      ca.acc = fa.acc;
+      ca.seg_end = fa.seg_end;
+      ca.seg_rs = fa.seg_rs;
+      ca.dst_vid = fa.dst_vid;
+      ca.out = fa.out[0];
+      ca.region_base = region_base;
+      ca.blk_rows = fa.blk_rows;
+      ca.stat_e = fa.stat_e;
+      ca.stat_n = fa.stat_n;
+      ca.err_flag = fa.err_flag;
+      ca.full_rp = fa.full_rp;
+      ca.ids = fa.ids;
+      ca.visible = fa.visible;
+      le = launch_final_copy(ca, grid.x, w->stream);
+    } else {
+      le = launch_final_dst(fa, fp.fast.has_where ? fp.fast.wbytes : 0, one, grid.x, w->stream);
+    }
     if (le != hipSuccess) {
       prof_end(w, p, K_EXPAND_FINAL, step, tix, 0.0, 0.0);   // (the profile's open event closed)
       return le;

@@ -412,6 +412,26 @@ struct FinalDstArgs {
 };
 hipError_t launch_final_dst(const FinalDstArgs& a, int wbytes, bool one, unsigned grid, hipStream_t s);
 
+// The final step over a statement index whose only YIELD is _dst (finalcopy.hip): a segmented
+// copy.  Every edge of the list passes, so output row e of [0, total) is known in advance: rows go
+// to out[region_base + e] in list order, one dense run.
+struct FinalCopyArgs {
+  const unsigned long long* acc;
+  const uint32_t* seg_end;
+  const uint32_t* seg_rs;
+  const int64_t* dst_vid;
+  int64_t* out;
+  uint64_t region_base;
+  uint32_t* blk_rows;              // [grid]: the run's length at 0, zero elsewhere
+  unsigned long long* stat_e;      // E_N over full_rp / ids / visible, as k_final_dst sums it
+  unsigned long long* stat_n;
+  unsigned long long* err_flag;    // QState::err (SPLIT_BAD)
+  const uint32_t* full_rp;
+  const uint32_t* ids;
+  const uint8_t* visible;
+};
+hipError_t launch_final_copy(const FinalCopyArgs& a, unsigned grid, hipStream_t s);
+
 // A prepared statement's filtered adjacency over one OVER type (stmtidx.hip): the type's rows
 // restricted to the edges passing the statement's WHERE `col <cmp> const`, original order kept.
 struct StmtIndexSpec {
