@@ -641,14 +641,16 @@ def ladder_cells(high: bool):
     return out
 
 
-def value_table(nan: bool = True, rows: int = 2400, seed: int = 5) -> Table:
+def value_table(nan: bool = True, rows: int = 2400, seed: int = 5, per_src: Optional[int] = None) -> Table:
     """The value-domain table: i (INT: the extremes, a byte ladder at either end of the order, full-
     range filler between), x (DOUBLE bit patterns: every special of both signs and the NaNs, finite
     filler), d (VID, both signs and the extremes), s (STRING, a function of d), t (TIMESTAMP), b
     (BOOL), z (DOUBLE, zeros of both signs only), c (a constant INT) and g (INT group labels:
     G_SPECIAL for a row whose x is a special, G_FINITE + 0..2 for finite filler, and the small
     dedicated groups appended at the end).  Every special is present three times.  nan=False: the
-    NaN cells are ordinary values (for the plain-Python models, whose max() / sort break on NaN)."""
+    NaN cells are ordinary values (for the plain-Python models, whose max() / sort break on NaN).
+    per_src: that many consecutive rows per source instead of the layout below (1: row `pos` is the
+    only out-edge of source SRC0 + pos)."""
     rng = np.random.default_rng(seed)
     reps = 3
     u64 = (1 << 64) - 1
@@ -701,6 +703,8 @@ def value_table(nan: bool = True, rows: int = 2400, seed: int = 5) -> Table:
         ("c", INT, np.full(rows + ne, 7)),
         ("g", INT, np.concatenate([g_col, np.array([e[0] for e in extra], np.int64)])),
     ]
+    if per_src is not None:
+        return Table(cols, per_src=per_src)
     # 61 rows per source; every dedicated group has a source of its own (EXTRA_SRC0 + g)
     return Table(cols, src=np.concatenate([np.arange(rows) // 61, EXTRA_SRC0 + np.array([e[0] for e in extra])]))
 

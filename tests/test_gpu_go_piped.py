@@ -1,9 +1,19 @@
-"""nbg_go_piped on the MI355X: `| GO FROM $-.col` over device-resident rows, judged by the host route
-on the same engine — nbg_rows_fetch of the input, then nbg_go with `starts' set to the fetched FROM
-column and the fetched table as its $- input — never by the piped call itself.  Rows compare as
-sorted rows; the step statistics and the edges scanned are compared too.  Where the reference's own
-answer is one of several ($- props after two or more steps: the backtracker's roots), the rows are
-checked against the admissible sets of tests/test_gpu_backtracker.py.
+"""nbg_go_piped on the MI355X: `| GO FROM $-.col` over device-resident rows.
+
+Who judges what.  The rows of a piped call are judged by the storage oracle (tests/support/
+oracle.py, pinned by the golden vectors of tests/test_oracle_golden.py): the input is fetched, and
+`Oracle.go(starts = the fetched FROM column, ..., inputs = the fetched table)` over the same KV
+records gives the expected rows, which compare as sorted rows, cell kinds included.  The oracle
+shares nothing with the engine: not the OP_INPUT lookup, not the interpreter's typing of $- cells,
+not the hop and final kernels, DISTINCT or the statistics.  The engine's other route to the same
+statement (nbg_rows_fetch, then nbg_go with the fetched table as its $- input) is kept as a third
+witness of the rows, and it is the reference for what the oracle does not report: the step
+statistics, the edges scanned and the numeric status of an error (the oracle must fail too; its
+code space is its own).  For one-step calls over type `e` alone the statistics are also counted
+from the fixture's adjacency.  Where the reference's own answer is one of several ($- props after
+two or more steps: the backtracker's roots), the root column is checked against the admissible sets
+of tests/test_gpu_backtracker.py and the other columns against the oracle.  The 4 M-row input of
+test_more_chunks_than_the_grid is judged by numpy.
 
 The graph is a seeded RMAT-11 over 5 parts with type `e` (w INT, x DOUBLE, f FLOAT; each (src, dst)
 once), a second type `r` (i INT, s STRING) over every fourth edge, tag `t` (name STRING) on nine
@@ -25,6 +35,8 @@ import pytest
 
 from nebula_amd import Engine, LocalCluster, NbgError, _lib as L, expr as E, kvgen, rmat
 from nebula_amd.engine import DeviceRows
+from tests.support import setops
+from tests.support.oracle import Oracle, OracleError
 
 pytestmark = pytest.mark.gpu
 
@@ -99,7 +111,7 @@ def _kv():
 
 @pytest.fixture(scope="module")
 def ff():
-    """The engine and three inputs, computed once and left unchanged: `two` (a two-step GO of many
+    """The engine, the oracle over the same records and three inputs, computed once and left unchanged: `two` (a two-step GO of many
     short segments with the same vid in many rows), `one` (a one-step GO with INT, DOUBLE and STRING
     payload columns) and `fan` (2,048 rows, one per leaf)."""
     kb, out, verts, roots = _kv()
@@ -107,11 +119,16 @@ def ff():
     f.out, f.verts, f.roots = out, verts, roots
     f.vertset = set(verts) | {NEG, IMIN, IMAX, INVIS, FAN} | set(range(LEAF0, LEAF0 + OB_CHUNK)) | set(range(END0, END0 + OB_CHUNK))
     f.eng = Engine(PARTS)
-    f.eng.register_edge(1, "e", E_SCHEMA)
-    f.eng.register_edge(2, "r", R_SCHEMA)
-    f.eng.register_tag(7, "t", T_SCHEMA)
-    f.eng.register_tag(8, "c", C_SCHEMA)
-    f.eng.load_builder(kb)
+    f.orc = Oracle(PARTS)
+    f.orc_calls = 0
+    for be, reg_e, reg_t in ((f.eng, f.eng.register_edge, f.eng.register_tag),
+                             (f.orc, lambda *a: f.orc.register(True, *a), lambda *a: f.orc.register(False, *a))):
+        reg_e(1, "e", E_SCHEMA)
+        reg_e(2, "r", R_SCHEMA)
+        reg_t(7, "t", T_SCHEMA)
+        reg_t(8, "c", C_SCHEMA)
+        be.load_builder(kb)
+    f.vert_arr = np.array(sorted(f.vertset), np.int64)
     f.two = f.eng.go_device(roots, [1], 2, b"", ID_S_W)
     f.two_rows = f.two.fetch()
     nseg = f.eng.lib.nbg_rows_num_segments(f.two.h)
@@ -147,6 +164,8 @@ def ff():
     for r in (f.two, f.one, f.fan):
         r.free()
     f.eng.close()
+    f.orc.close()
+    assert f.orc_calls > 0, "no call reached the oracle"
 
 
 def _take(rows):
@@ -163,7 +182,26 @@ def _code(fn):
 
 
 def _sorted(rows):
-    return sorted((tuple(r) for r in rows), key=repr)
+    """Rows as sorted tuples of (kind, value) cells, doubles by their bits: True is not 1."""
+    return sorted((tuple(setops.bits_cell(v) for v in r) for r in rows), key=repr)
+
+
+def _oracle(f, fetched, names, col, etypes, steps=1, where=b"", yields=(), distinct=False, over_all=False):
+    """The oracle's rows of the piped statement over the fetched table (an OracleError passes through)."""
+    f.orc_calls += 1
+    starts = [r[names.index(col)] for r in fetched]
+    return f.orc.go(starts, etypes, steps, where, list(yields), distinct, over_all, inputs=(names, fetched, col))
+
+
+def _counted(f, fetched, names, col, distinct):
+    """([frontier], [edges]) of one step over type `e` from the fixture's adjacency: the starts that
+    are vertices (INVIS is one, with no visible edge) and their out-degrees; DISTINCT starts once per vid."""
+    starts = [r[names.index(col)] for r in fetched]
+    if distinct:
+        starts = sorted(set(starts))
+    fr = int(np.isin(np.array(starts, np.int64), f.vert_arr).sum()) if starts else 0
+    ed = sum(len(f.out[v]) for v in starts if v in f.out and v != INVIS)
+    return [fr], [ed]
 
 
 def _host_route(f, fetched, names, col, etypes, steps=1, where=b"", yields=(), distinct=False, over_all=False):
@@ -177,19 +215,27 @@ def _host_route(f, fetched, names, col, etypes, steps=1, where=b"", yields=(), d
 
 
 def _parity(f, rows, names, col, etypes, steps=1, where=b"", yields=(), distinct=False, over_all=False, fetched=None):
-    """The piped call equals the host route: rows, statistics and status.  Returns the rows."""
+    """The piped call against the oracle (rows, or that it fails) and against the engine's host route
+    (rows, statistics and status); one step over `e` alone: the statistics as counted.  Returns the rows."""
     fetched = rows.fetch() if fetched is None else fetched
     want, stats = _host_route(f, fetched, names, col, etypes, steps, where, yields, distinct, over_all)
     if stats is None:
+        with pytest.raises(OracleError):
+            _oracle(f, fetched, names, col, etypes, steps, where, yields, distinct, over_all)
         assert _code(lambda: f.eng.go_piped(rows, names, col, etypes, steps, where, list(yields), distinct, over_all)) == want
         return None
+    judge = _oracle(f, fetched, names, col, etypes, steps, where, yields, distinct, over_all)
     got = f.eng.go_piped(rows, names, col, etypes, steps, where, list(yields), distinct, over_all)
     try:
         fr, ed = got.step_stats()
         assert (fr, ed, got.edges_scanned) == tuple(stats)
+        if list(etypes) == [1] and steps == 1 and not over_all:
+            counted = _counted(f, fetched, names, col, distinct)
+            assert (fr, ed) == (counted if counted[0][0] else ([], [])) and got.edges_scanned == sum(ed)
         dev = got.fetch()
     finally:
         got.free()
+    assert len(dev) == len(judge) and _sorted(dev) == _sorted(judge)
     assert len(dev) == len(want) and _sorted(dev) == _sorted(want)
     return dev
 
@@ -214,11 +260,11 @@ CASES = {
                                      E.binop("/", ip("x"), E.const(4.0)).encode()]),
     "input_in_where": dict(where=E.binop("&&", E.binop(">", ip("w"), E.const(0)), E.binop("<", ep("e", "w"), ip("w"))).encode(),
                            yields=[ip("w").encode(), ep("e", "w").encode()]),
-    # (some sources of `one` carry no tag: both routes answer these two with the same error;
+    # (some sources of `one` carry no tag: the oracle and both routes answer these two with an error;
     # test_tag_props_over_tagged_sources has the rows)
     "tag_props_untagged_source": dict(yields=[E.src_prop("t", "name").encode(), E.dst_prop("c", "pop").encode(), ep("e", "_dst").encode()]),
     "tag_props_untagged_source_and_input": dict(yields=[E.dst_prop("t", "name").encode(), ip("nm").encode(), E.src_prop("c", "pop").encode()]),
-    "input_prop_missing": dict(yields=[ip("nope").encode()]),               # an evaluation error on both routes
+    "input_prop_missing": dict(yields=[ip("nope").encode()]),               # an evaluation error everywhere
     "two_types_input": dict(etypes=[1, 2], yields=[ip("w").encode(), ep("e", "w").encode(), ep("r", "s").encode()]),
 }
 
@@ -226,6 +272,7 @@ CASES = {
 @pytest.mark.parametrize("distinct", [False, True])
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_parity_with_the_host_route(ff, name, distinct):
+    """(The name is older than its judge: _parity compares with the oracle first, then with the host route.)"""
     kw = dict(etypes=[1], steps=1, where=b"", yields=(), over_all=False)
     kw.update(CASES[name])
     dev = _parity(ff, ff.one, ff.one_names, "id", kw["etypes"], kw["steps"], kw["where"], kw["yields"], distinct, kw["over_all"],
@@ -277,10 +324,11 @@ def _admissible(out, roots, steps):
 @pytest.mark.parametrize("steps", [2, 3])
 def test_input_props_after_several_steps_are_admissible(ff, steps, distinct):
     """`GO N STEPS FROM $-.id OVER e YIELD $-.id, e._src, e._dst`: the root each row names is one its
-    source's backtracker may hold; the rows without the root column are exact."""
+    source's backtracker may hold; the rows without the root column are exact, and the oracle's."""
     ys = [ip("id").encode(), ep("e", "_src").encode(), ep("e", "_dst").encode()]
     got = ff.eng.go_piped(ff.one, ff.one_names, "id", [1], steps, b"", ys, distinct)
-    want, stats = _host_route(ff, ff.one_rows, ff.one_names, "id", [1], steps, b"", ys, distinct)
+    judge = _oracle(ff, ff.one_rows, ff.one_names, "id", [1], steps, b"", ys, distinct)
+    host, stats = _host_route(ff, ff.one_rows, ff.one_names, "id", [1], steps, b"", ys, distinct)
     fr, ed = got.step_stats()
     assert (fr, ed, got.edges_scanned) == tuple(stats)
     dev = _take(got)
@@ -288,10 +336,11 @@ def test_input_props_after_several_steps_are_admissible(ff, steps, distinct):
     A = _admissible(ff.out, roots, steps)
     assert dev and max(len(x) for x in A.values()) > 1
     assert all(r[0] in A.get(r[1], ()) for r in dev)
-    if not distinct:
-        assert _sorted([r[1:] for r in dev]) == _sorted([r[1:] for r in want])
-    else:
-        assert {tuple(r[1:]) for r in dev} == {tuple(r[1:]) for r in want}
+    for want in (judge, host):
+        if not distinct:
+            assert _sorted([r[1:] for r in dev]) == _sorted([r[1:] for r in want])
+        else:
+            assert {tuple(r[1:]) for r in dev} == {tuple(r[1:]) for r in want}
 
 
 # ------------------------------------------------------------------------------ 2. the last row of a vid wins
@@ -372,15 +421,19 @@ def test_input_sizes(ff, n, distinct):
 
 
 def test_many_short_segments(ff):
-    """The whole two-step result (its segments as they lie), without $-: the rows by their digest
-    against nbg_go_device from the fetched column."""
+    """The whole two-step result (its segments as they lie), without $-: the sorted rows against the
+    oracle's, and by their digest against nbg_go_device from the fetched column."""
     starts = [r[0] for r in ff.two_rows]
+    ys = [ep("e", "_dst").encode(), ep("e", "w").encode()]
     for distinct in (False, True):
-        want = ff.eng.go_device(starts, [1], 1, W_LT, [ep("e", "_dst").encode(), ep("e", "w").encode()], distinct)
-        got = ff.eng.go_piped(ff.two, NAMES, "id", [1], 1, W_LT, [ep("e", "_dst").encode(), ep("e", "w").encode()], distinct)
+        judge = _oracle(ff, ff.two_rows, NAMES, "id", [1], 1, W_LT, ys, distinct)
+        want = ff.eng.go_device(starts, [1], 1, W_LT, ys, distinct)
+        got = ff.eng.go_piped(ff.two, NAMES, "id", [1], 1, W_LT, ys, distinct)
         try:
             assert got.count == want.count > 0 and got.digest() == want.digest()
             assert got.step_stats() == want.step_stats() and got.edges_scanned == want.edges_scanned
+            assert got.step_stats() == _counted(ff, ff.two_rows, NAMES, "id", distinct)
+            assert got.count == len(judge) and _sorted(got.fetch()) == _sorted(judge)
         finally:
             got.free()
             want.free()
@@ -410,6 +463,13 @@ def test_more_chunks_than_the_grid(ff):
         try:
             assert got.count == want.count == n and got.digest() == want.digest()
             assert got.step_stats() == want.step_stats() and got.edges_scanned == want.edges_scanned == n
+            # by numpy: every input cell gives one row, the row of its leaf
+            k = np.asarray(cells) - LEAF0
+            gid, gdst, gw = got.fetch_bits(copy=False)
+            assert k.min() == 0 and k.max() == OB_CHUNK - 1 and len(gid) == n
+            assert gid.min() >= LEAF0 and gid.max() < LEAF0 + OB_CHUNK
+            assert np.array_equal(np.bincount(gid - LEAF0, minlength=OB_CHUNK), np.bincount(k, minlength=OB_CHUNK))
+            assert np.array_equal(gdst, END0 + (gid - LEAF0)) and np.array_equal(gw, (gid - LEAF0) % 100 - 50)
         finally:
             got.free()
             want.free()
@@ -444,18 +504,24 @@ def test_inputs_from_every_stage(ff):
 
 def test_three_sentence_pipe(ff):
     """`GO FROM r OVER e YIELD e._dst AS id | GO FROM $-.id OVER e YIELD e._dst AS id | GO FROM $-.id
-    OVER r YIELD $-.id, r.s`: go_piped into go_piped, against three host calls."""
+    OVER r YIELD $-.id, r.s`: go_piped into go_piped.  Each sentence against the oracle, fed the table
+    the sentence before it left (fetched), and the last against three host calls."""
     ys = [ep("e", "_dst").encode()]
     first = ff.eng.go_device(ff.roots, [1], 1, b"", ys)
     second = ff.eng.go_piped(first, ["id"], "id", [1], 1, b"", ys)
     try:
+        ff.orc_calls += 1
+        t1, t2 = first.fetch(), second.fetch()
+        assert t1 and _sorted(t1) == _sorted(ff.orc.go(ff.roots, [1], 1, b"", ys))
+        assert _sorted(t2) == _sorted(_oracle(ff, t1, ["id"], "id", [1], 1, b"", ys))
         h1 = ff.eng.go(ff.roots, [1], 1, b"", ys)
         h2 = ff.eng.go([r[0] for r in h1], [1], 1, b"", ys)
         assert second.count == len(h2) > INLINE_STARTS
         last = [ip("id").encode(), ep("r", "s").encode()]
         third = _take(ff.eng.go_piped(second, ["id"], "id", [2], 1, b"", last))
+        assert third and _sorted(third) == _sorted(_oracle(ff, t2, ["id"], "id", [2], 1, b"", last))
         h3 = ff.eng.go([r[0] for r in h2], [2], 1, b"", last, inputs=(["id"], h2, "id"))
-        assert third and _sorted(third) == _sorted(h3)
+        assert _sorted(third) == _sorted(h3)
     finally:
         first.free()
         second.free()
@@ -464,7 +530,7 @@ def test_three_sentence_pipe(ff):
 def test_output_feeds_every_stage(ff):
     ys = [ep("e", "_dst").encode(), ep("e", "_src").encode(), ep("e", "w").encode()]
     out = ff.eng.go_piped(ff.one, ff.one_names, "id", [1], 1, b"", ys)
-    want, _ = _host_route(ff, ff.one_rows, ff.one_names, "id", [1], 1, b"", ys)
+    want = _oracle(ff, ff.one_rows, ff.one_names, "id", [1], 1, b"", ys)        # (every stage below is judged by these rows)
     try:
         assert out.count == len(want) > OB_CHUNK
         g = _take(ff.eng.group_by(out, NAMES, [ip("s").encode()], [("", ip("s").encode(), "s"), ("COUNT", E.const("*").encode(), "n")]))
@@ -653,6 +719,9 @@ def test_status_7_evaluation_errors_as_nbg_go(ff):
     ys = [E.binop("/", E.const(7), E.binop("-", ip("w"), ep("e", "w"))).encode()]      # fails where $-.w == e.w
     want, stats = _host_route(ff, ff.one_rows, ff.one_names, "id", [1], 1, b"", ys)
     assert want == L.E_EXECUTION_ERROR and stats is None
+    for distinct in (False, True):
+        with pytest.raises(OracleError):
+            _oracle(ff, ff.one_rows, ff.one_names, "id", [1], 1, b"", ys, distinct)
     assert _code(lambda: ff.eng.go_piped(ff.one, ff.one_names, "id", [1], 1, b"", ys)) == L.E_EXECUTION_ERROR
     assert _code(lambda: ff.eng.go_piped(ff.one, ff.one_names, "id", [1], 1, b"", ys, True)) == L.E_EXECUTION_ERROR
 
