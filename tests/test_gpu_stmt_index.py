@@ -19,8 +19,8 @@ pytestmark = pytest.mark.gpu
 DST = E.edge_prop("e", "_dst").encode()
 
 
-def where(op, c, const_left=False):
-    col, k = E.edge_prop("e", "w"), E.const(int(c))
+def where(op, c, const_left=False, col="w"):
+    col, k = E.edge_prop("e", col), E.const(int(c))
     return (E.binop(op, k, col) if const_left else E.binop(op, col, k)).encode()
 
 
