@@ -163,6 +163,17 @@ extern "C" {
  *   an input of 2^32 rows or more.
  *   nbg_go's own limits stay, among them the 2^32 - 1 bound on the start list's entries plus edges,
  *   which a piped list with duplicated hubs reaches easily (YIELD DISTINCT de-duplicates the list).
+ * nbg_rows_encode (tests/test_gpu_rows_encode.py holds one test per limit a GO result can reach; the
+ * mixed-kind column, the kind its type does not read, the row count and the 4 GiB row are guards no
+ * test reaches):
+ *   a partitioned engine (num_gpus > 1): its rows live on several ranks;
+ *   an input whose row schema re-reads its columns (a misaligned or FLOAT column);
+ *   a column whose value kind differs between OVER types (col_kind == -1), or is not the kind its
+ *   type's reader takes (no aligned result has one);
+ *   a string column that can hold strings outside the dictionary other than a per-OVER-type
+ *   constant (a non-empty derived table);
+ *   an input of 2^32 rows or more; a schema and dictionary under which one row could encode to
+ *   4 GiB or more (a row's length is a 32-bit word between the passes).
  * (A storage filter with a function call is E_INVALID_FILTER per part, as checkExp answers it,
  * QueryBaseProcessor.inl:172-290.)
  * Not limits: $- / $var input strings absent from the snapshot's dictionary, string functions
@@ -965,6 +976,60 @@ typedef struct {
 } nbg_fetch_edges_request;
 int32_t nbg_fetch_edges(nbg_engine* e, const nbg_rows* in, const nbg_fetch_edges_request* req, nbg_rows** out);
 
+/* ---- RowSetWriter bytes of a device-resident result (InterimResult's form) -----------------
+ * What graphd makes of every result before the next executor, the client or a fallback path sees
+ * it: an InterimResult, i.e. a schema plus the RowSetWriter bytes of every row
+ * (GoExecutor.cpp:707-779, InterimResult.cpp:602-640).  nbg_rows_encode produces those bytes where
+ * the rows lie and delivers them in pinned host memory, so the caller adds them with
+ * RowSetWriter::addAll and builds the schema from nbg_rowset_col_type and its own column names;
+ * no row passes through a RowWriter on the host.
+ * Input: a device-resident result of the same single engine: a GO result (nbg_go_device,
+ * nbg_go_execute with device = 1, nbg_go_wait, nbg_go_piped) or the output of any stage above.  It
+ * stays valid and unchanged.  The call runs under the engine lock on the engine's stream; its
+ * scratch and the device copy of the bytes are released before it returns.  The result does not
+ * depend on `in` after the call; it must be freed (nbg_rowset_free) before nbg_destroy.
+ * The bytes (byte-exact): the concatenation, in `in`'s fetch order (segment order, the order
+ * nbg_rows_fetch delivers), of varint(len(row)) + row for every row (RowSetWriter.cpp:21-33), with
+ * row = RowWriter(schema) << cell_0 << ...; encode() under schema version 0 (RowWriter.cpp:26-95,
+ * RowWriter.inl:9-45):
+ *   header   one byte, offsetBytes - 1, with offsetBytes = calcOccupiedBytes(cord size): 1 below 256
+ *            bytes of cord, 2 below 65,536, 3 above; set whether or not the row has offsets;
+ *   offsets  the cord's size after column 16 and after column 32 (RowWriter.h:143-148), each
+ *            offsetBytes wide, little endian: 0, 1 or 2 of them (NBG_MAX_YIELDS is 32);
+ *   cord     the cells by nbg_rows_col_type: INT / TIMESTAMP folly::encodeVarint of the payload as
+ *            uint64_t (a negative value takes 10 bytes); VID 8 bytes, little endian; DOUBLE the 8
+ *            payload bytes; BOOL one byte, 0 or 1; STRING varint(length), then the bytes — the
+ *            dictionary's for a dictionary code, else the constant outside the dictionary that the
+ *            cell's OVER type spells in that column.
+ * The stored value of an aligned result is what InterimResult::getRows took back from the written
+ * row (go.cpp prepare_schema), so encoding the stored cell by the column's type reproduces what
+ * RowWriter wrote: a BOOL written into an INT column was one zero byte, is stored as INT 0 and is
+ * written as varint 0, the same byte.
+ * Statuses, in this order:
+ *  1. NBG_E_INVALID_ARGUMENT: a null argument; `in` of another engine or host-only.
+ *  2. NBG_E_UNSUPPORTED: a partitioned engine (each rank's rows could be encoded rank-locally and
+ *     joined with RowSetWriter::addAll; not built).
+ *  3. `in` has no rows: NBG_OK, a rowset of len 0 and rows 0 (nbg_rowset_data is NULL) that still
+ *     reports the columns' types.
+ *  4. Device scope: see "Device limits" (NBG_E_UNSUPPORTED; the caller then fetches `in` and runs
+ *     its RowWriter loop).
+ *  5. NBG_E_OUT_OF_MEMORY: a device or pinned allocation failed.
+ * Three launches (DESIGN.md "RowSet encoding of device rows"): the rows' lengths, an exclusive scan
+ * of the per-chunk byte sums (one 8-byte readback sizes the output), and the encoding through an
+ * LDS staging buffer that is streamed out 16 bytes per lane. */
+typedef struct nbg_rowset nbg_rowset;
+int32_t nbg_rows_encode(nbg_engine* e, const nbg_rows* in, nbg_rowset** out);
+const uint8_t* nbg_rowset_data(const nbg_rowset* rs);       /* pinned host memory, RowSetWriter::data() */
+uint64_t nbg_rowset_len(const nbg_rowset* rs);
+int64_t  nbg_rowset_rows(const nbg_rowset* rs);
+int32_t  nbg_rowset_num_cols(const nbg_rowset* rs);
+int32_t  nbg_rowset_col_type(const nbg_rowset* rs, int32_t col);   /* NBG_T_*: the SchemaWriter's field type; -1 out of range */
+void     nbg_rowset_free(nbg_rowset* rs);
+/* NBG_T_* of a result column (Collector::getSchema's type, what the row's writer and reader go by):
+ * the result schema's entry, or the kind's natural type where it names none (INT, DOUBLE, BOOL,
+ * STRING; the rule of nbg_set_op's checkSchema above); -1 out of range. */
+int32_t  nbg_rows_col_type(const nbg_rows* r, int32_t col);
+
 /* ---- FIND SHORTEST | ALL PATH (FindPathExecutor semantics) ----------------------------- */
 typedef struct {
   const int64_t* from;           /* de-duplicated by the callee (VerticesClause::prepare)    */
@@ -1120,6 +1185,8 @@ typedef struct {
  * its COUNT_DISTINCT columns are counted under nbg_yield's and nbg_set_op's kernels. */
 /* ... and nbg_go_piped's: k_gp_resolve, k_gp_table, k_gp_degrees, k_gp_emit, k_gp_compact (DESIGN.md
  * "GO over device rows"); the hops after them are counted under nbg_go's kernels. */
+/* ... and nbg_rows_encode's: k_re_size, k_re_scan, k_re_emit (DESIGN.md "RowSet encoding of device
+ * rows"); k_re_emit's algorithmic bytes are the cells and row lengths read plus the bytes written. */
 /* ---- FIND PATH replica of a partitioned engine (replica.hip) ---------------------------------
  * A partitioned engine (num_gpus > 1) also builds, at nbg_finalize (collectively), a replica of
  * every rank's path CSRs (offsets, neighbour ids and vids, ranks; no property columns) when it fits

@@ -168,6 +168,14 @@ SIGNATURES = [
     ("nbg_yield_agg", i32, [vp, vp, P(nbg_yield_request), P(vp)]),
     ("nbg_fetch_vertices", i32, [vp, vp, P(nbg_fetch_request), P(vp)]),
     ("nbg_fetch_edges", i32, [vp, vp, P(nbg_fetch_edges_request), P(vp)]),
+    ("nbg_rows_col_type", i32, [vp, i32]),
+    ("nbg_rows_encode", i32, [vp, vp, P(vp)]),
+    ("nbg_rowset_data", P(u8), [vp]),
+    ("nbg_rowset_len", u64, [vp]),
+    ("nbg_rowset_rows", i64, [vp]),
+    ("nbg_rowset_num_cols", i32, [vp]),
+    ("nbg_rowset_col_type", i32, [vp, i32]),
+    ("nbg_rowset_free", None, [vp]),
     ("nbg_find_path", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_submit", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_wait", i32, [vp, P(vp)]),

@@ -75,6 +75,7 @@ struct Engine {
   StageProf<FV_KINDS> fv_prof;                       // nbg_fetch_vertices' kernels
   StageProf<FE_KINDS> fe_prof;                       // nbg_fetch_edges' kernels
   StageProf<GP_KINDS> gp_prof;                       // nbg_go_piped's kernels
+  StageProf<RE_KINDS> re_prof;                       // nbg_rows_encode's kernels
   // pinned host blocks of fetched GO rows (nbg_rows_fetch), reused across queries
   std::mutex pinned_mu;
   std::vector<std::pair<size_t, void*>> pinned_free;
@@ -180,6 +181,7 @@ void for_stage_profs(Eng& E, F f) {
   f(kFeKernelNames, E.fe_prof);   // nbg_fetch_edges' (fetchedges.hip)
   f(kYaKernelNames, E.ya_prof);   // nbg_yield_agg's (yieldagg.hip)
   f(kGpKernelNames, E.gp_prof);   // nbg_go_piped's (gopipe.hip)
+  f(kReKernelNames, E.re_prof);   // nbg_rows_encode's (rowenc.hip)
 }
 
 int32_t engine_ready(Engine& E);   // workspace (+ partition buffers) after finalize / snapshot load

@@ -1119,6 +1119,34 @@ hipError_t gopipe_list(GoPipe* p, Workspace* ws, uint32_t* host);
 hipError_t gopipe_index(GoPipe* p, uint32_t mask, int ncols, int64_t** in_ids, std::vector<int64_t*>* cols);
 void gopipe_close(GoPipe* p);
 
+// ---- RowSetWriter bytes of device rows (rowenc.hip; RowWriter.cpp:26-95, RowWriter.inl:9-45,
+// RowSetWriter.cpp:21-33).  Every row becomes varint(len(row)) + row with row = header byte, block
+// offsets, cord, the cells written by the column's NBG_T_* type (DESIGN.md "RowSet encoding of
+// device rows").
+// A tile of RE_TILE rows whose bytes fit the staging buffer is encoded into LDS and streamed out
+// 16 bytes per lane; a larger one is cut into its waves' 64 rows, each staged the same way when it
+// fits and else (long strings) stored directly, a wave per row.
+constexpr uint32_t RE_STAGE_BYTES = 16 * 1024;
+struct RePlan {
+  int ncols = 0;
+  uint8_t type[MAX_YIELDS] = {};     // NBG_T_* per column: how a cell is written
+  DevStrings str;                    // the dictionary (off / bytes / n)
+  std::vector<uint8_t> chunk_type;   // re_chunk_types (rowenc.h): the OVER position of each chunk
+  std::vector<uint32_t> koff;        // re_const_table: entry t * ncols + c, the constant outside
+  std::vector<char> kbytes;          //   the dictionary OVER position t spells in column c
+};
+// nbg_profile_read's entries (kReKernelNames), timed while nbg_profile mode 1 is on
+enum ReKernel { RE_K_SIZE = 0, RE_K_SCAN, RE_K_EMIT, RE_KINDS };
+extern const char* const kReKernelNames[RE_KINDS];
+// Encodes the rows of `inw` listed by segs (first row, rows), in that order, into a device buffer
+// and copies it into `host` in one DMA: `grow(bytes)` is called once, after the sizing pass, and
+// returns pinned host memory of at least that many bytes (nullptr: NBG_E_OUT_OF_MEMORY).
+// Synchronous; every device allocation is released before it returns.  NBG_OK,
+// NBG_E_OUT_OF_MEMORY or NBG_E_DEVICE (*err names the failing call).
+int32_t ws_rows_encode(Workspace* inw, hipStream_t stream, const std::vector<std::pair<uint64_t, uint64_t>>& segs,
+                       const RePlan& plan, void* (*grow)(void* ctx, uint64_t bytes), void* ctx, uint64_t* len,
+                       StageProf<RE_KINDS>* prof, std::string* err);
+
 // Query pipeline (all asynchronous on the workspace stream until ws_end_query):
 hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, const std::vector<TypeProgram>* progs,
                           uint64_t stmt_id);

@@ -15,6 +15,17 @@ uint64_t query_rand_seed();   // a fresh seed for each query's rand32 / rand64 s
 enum WClass : uint8_t { W_ID = 0, W_ONE = 1, W_EIGHT = 2 };
 }
 
+// The result of nbg_rows_encode (stages.cpp): the RowSetWriter bytes in pinned memory from the
+// engine's pool, and the schema's field types.
+struct nbg_rowset {
+  nbg::Engine* eng = nullptr;
+  uint8_t* data = nullptr;
+  size_t cap = 0;                // the pinned block's size (returned to the pool with it)
+  uint64_t len = 0;
+  uint64_t rows = 0;
+  std::vector<int32_t> types;    // NBG_T_* per column
+};
+
 struct nbg_rows {
   struct Seg {
     uint64_t begin = 0, end = 0;

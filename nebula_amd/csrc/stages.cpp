@@ -1,7 +1,8 @@
 // The stages over device-resident rows at the C ABI (include/nbg.h): nbg_group_by, nbg_order_by,
-// nbg_set_op, nbg_yield, nbg_yield_agg, nbg_fetch_vertices and nbg_fetch_edges.  Each plans its
-// request on the host, as its executor in the reference checks it, and hands the plan to its driver
-// (groupby.hip, orderby.hip, setops.hip, yieldrows.hip, yieldagg.hip, fetchrows.hip, fetchedges.hip).
+// nbg_set_op, nbg_yield, nbg_yield_agg, nbg_fetch_vertices, nbg_fetch_edges and nbg_rows_encode.  Each
+// plans its request on the host, as its executor in the reference checks it, and hands the plan to its
+// driver (groupby.hip, orderby.hip, setops.hip, yieldrows.hip, yieldagg.hip, fetchrows.hip,
+// fetchedges.hip, rowenc.hip).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -9,6 +10,7 @@
 #include <set>
 
 #include "nbg_rows.h"
+#include "rowenc.h"
 
 using namespace nbg;
 
@@ -62,13 +64,17 @@ int32_t copy_input_names(Engine& E, const std::string& label, const char* const*
 struct DeviceInput {
   Workspace* w = nullptr;
   Segs segs;
+  std::vector<int> types;   // each segment's OVER position (nbg_rows::Seg::type)
 };
 int32_t device_input(Engine& E, const std::string& label, const nbg_rows* in, DeviceInput* d) {
   if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
   auto* m = const_cast<nbg_rows*>(in);
   m->build_segs();
   for (auto& sg : m->segs)
-    if (sg.end > sg.begin) d->segs.emplace_back(sg.begin, sg.end - sg.begin);
+    if (sg.end > sg.begin) {
+      d->segs.emplace_back(sg.begin, sg.end - sg.begin);
+      d->types.push_back(sg.type);
+    }
   d->w = in->owned_ws ? in->owned_ws : in->ws;
   return d->w ? NBG_OK : E.fail(NBG_E_INVALID_ARGUMENT, label + ": the rows have no device workspace");
 }
@@ -1533,6 +1539,108 @@ int32_t nbg_fetch_edges(nbg_engine* h, const nbg_rows* in, const nbg_fetch_edges
   if (ow) adopt_rows(res.get(), ow, n, ny);
   *out = res.release();
   return NBG_OK;
+}
+
+// ============================================================================= RowSet encoding
+// What GoExecutor::setupInterimResult (GoExecutor.cpp:707-779) and InterimResult (InterimResult.cpp:
+// 602-640) make of a result: the schema's field types and the RowSetWriter bytes of every row; the
+// kernels are in rowenc.hip.
+int32_t nbg_rows_col_type(const nbg_rows* r, int32_t col) {
+  if (!r || col < 0 || col >= r->ncols) return -1;
+  return InputCols(r).type[col];
+}
+
+int32_t nbg_rows_encode(nbg_engine* h, const nbg_rows* in, nbg_rowset** out) {
+  if (!h || !in || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  // ---- 1., 2.
+  if (int32_t rc = guard_rows(E, "rows encode", {in})) return rc;
+  if (int32_t rc = guard_partitioned(E, "rows encode")) return rc;
+  const int nc = in->ncols;
+  const InputCols cols(in);
+  auto res = std::make_unique<nbg_rowset>();
+  res->eng = &E;
+  res->types = cols.type;
+  // ---- 3.
+  if (!in->count) {
+    *out = res.release();
+    return NBG_OK;
+  }
+  // ---- 4. device scope
+  if (in->misaligned || in->float_col)
+    return E.fail(NBG_E_UNSUPPORTED, "rows encode: the input's row schema re-reads its columns (misaligned or FLOAT)");
+  if (nc < 1 || nc > MAX_YIELDS) return E.fail(NBG_E_INVALID_ARGUMENT, "rows encode: the rows have no columns");
+  if (cols.any_mixed) return E.fail(NBG_E_UNSUPPORTED, "rows encode: a column mixes value kinds between OVER types");
+  RePlan plan;
+  plan.ncols = nc;
+  std::vector<uint8_t> is_string(nc, 0);
+  uint64_t widest = 1 + 2 * 8;   // the header byte and two block offsets
+  for (int c = 0; c < nc; ++c) {
+    const int32_t t = cols.type[c];
+    if (t == NBG_T_FLOAT) return E.fail(NBG_E_UNSUPPORTED, "rows encode: a FLOAT column");
+    // (the cell is written by its type: a kind the type's reader would not take back is no aligned result)
+    const VKind reads = t == NBG_T_BOOL ? VK_BOOL : t == NBG_T_DOUBLE ? VK_DOUBLE : t == NBG_T_STRING ? VK_STRING : VK_INT;
+    if (cols.kind[c] != reads)
+      return E.fail(NBG_E_UNSUPPORTED, "rows encode: column " + std::to_string(c) + " holds another kind than its type reads");
+    plan.type[c] = (uint8_t)t;
+    is_string[c] = t == NBG_T_STRING;
+    if (is_string[c] && !in->derived.empty())
+      return E.fail(NBG_E_UNSUPPORTED, "rows encode: string column " + std::to_string(c) +
+                                           " can hold strings outside the dictionary (derived strings)");
+    uint64_t cell = 10;
+    if (is_string[c]) {
+      cell = E.refresh_max_dict_len();
+      for (auto& cs : in->const_str)
+        if (c < (int)cs.size()) cell = std::max<uint64_t>(cell, cs[c].size());
+      cell += 5;
+    }
+    widest += cell;
+  }
+  if (in->count > 0xFFFFFFFFull) return E.fail(NBG_E_UNSUPPORTED, "rows encode: an input of 2^32 rows or more");
+  if (widest + 10 > 0xFFFFFFFFull)   // (a row's length is a 32-bit word between the passes)
+    return E.fail(NBG_E_UNSUPPORTED, "rows encode: a row could encode to 4 GiB or more");
+  // ---- the segments in fetch order, each chunk's OVER position, the constants outside the dictionary
+  DeviceInput d;
+  if (int32_t rc = device_input(E, "rows encode", in, &d)) return rc;
+  for (int t : d.types)
+    if (t < 0 || t >= (int)in->const_str.size() || t > 255)
+      return E.fail(NBG_E_DEVICE, "rows encode: a segment of an unknown OVER position");
+  plan.chunk_type = re_chunk_types(d.segs, d.types, OB_CHUNK);
+  ReConsts consts = re_const_table(in->const_str, is_string, nc);
+  if (!consts.fits) return E.fail(NBG_E_UNSUPPORTED, "rows encode: 4 GiB or more of string constants");
+  plan.koff = std::move(consts.off);
+  plan.kbytes = std::move(consts.bytes);
+  plan.str = E.dev_strings();
+  // ---- 5. the passes
+  auto grow = [](void* ctx, uint64_t bytes) -> void* {
+    auto* rs = static_cast<nbg_rowset*>(ctx);
+    rs->data = static_cast<uint8_t*>(rs->eng->pinned_get((size_t)bytes, &rs->cap));
+    return rs->data;
+  };
+  std::string err;
+  const int32_t rc = ws_rows_encode(d.w, E.stream, d.segs, plan, grow, res.get(), &res->len, &E.re_prof, &err);
+  if (rc) {
+    if (res->data) E.pinned_put(res->data, res->cap);
+    return E.fail(rc, err);
+  }
+  res->rows = in->count;
+  *out = res.release();
+  return NBG_OK;
+}
+
+const uint8_t* nbg_rowset_data(const nbg_rowset* rs) { return rs ? rs->data : nullptr; }
+uint64_t nbg_rowset_len(const nbg_rowset* rs) { return rs ? rs->len : 0; }
+int64_t nbg_rowset_rows(const nbg_rowset* rs) { return rs ? (int64_t)rs->rows : 0; }
+int32_t nbg_rowset_num_cols(const nbg_rowset* rs) { return rs ? (int32_t)rs->types.size() : 0; }
+int32_t nbg_rowset_col_type(const nbg_rowset* rs, int32_t col) {
+  return rs && col >= 0 && col < (int32_t)rs->types.size() ? rs->types[col] : -1;
+}
+void nbg_rowset_free(nbg_rowset* rs) {
+  if (!rs) return;
+  if (rs->eng && rs->data) rs->eng->pinned_put(rs->data, rs->cap);
+  delete rs;
 }
 
 }  // extern "C"

@@ -14,7 +14,7 @@ import ctypes as C
 import os
 import weakref
 import struct
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -79,6 +79,25 @@ class DeviceRows:
             v = np.ctypeslib.as_array(self.eng.lib.nbg_rows_col_bits(self.h, c), shape=(n,))
             out.append(v.copy() if copy else v)
         return out
+
+    def col_types(self) -> List[int]:
+        """The NBG_T_* type of every column (nbg_rows_col_type): the result schema's field types."""
+        lib = self.eng.lib
+        return [lib.nbg_rows_col_type(self.h, c) for c in range(lib.nbg_rows_num_cols(self.h))]
+
+    def encode(self) -> Tuple[bytes, List[int]]:
+        """nbg_rows_encode: the RowSetWriter bytes of the rows, in fetch order, encoded where the
+        rows lie, and the schema's NBG_T_* field types — what an InterimResult is built from.  The
+        rows stay valid and unchanged."""
+        lib = self.eng.lib
+        out = C.c_void_p()
+        self.eng._check(lib.nbg_rows_encode(self.eng.h, self.h, C.byref(out)), "rows encode")
+        try:
+            n = lib.nbg_rowset_len(out)
+            data = C.string_at(lib.nbg_rowset_data(out), n) if n else b""
+            return data, [lib.nbg_rowset_col_type(out, c) for c in range(lib.nbg_rowset_num_cols(out))]
+        finally:
+            lib.nbg_rowset_free(out)
 
     def digest(self):
         """(rows, xor, sum) of the rows' splitmix64 chains, computed in HBM (nbg_rows_digest)."""
