@@ -30,6 +30,9 @@
  *   nbg_fetch_vertices         ≙ FetchVerticesExecutor over piped rows or a vid list
  *       (src/graph/FetchVerticesExecutor.cpp:19-311, src/graph/FetchExecutor.cpp:14-131)
  *   nbg_fetch_edges ≙ FetchEdgesExecutor (src/graph/FetchEdgesExecutor.cpp:17-384, src/graph/FetchExecutor.cpp:14-131, src/storage/QueryEdgePropsProcessor.cpp:17-101)
+ *   nbg_rows_encode ≙ GoExecutor::setupInterimResult / RowSetWriter (src/graph/GoExecutor.cpp:707-779)
+ *   nbg_rows_decode ≙ InterimResult::getRows / RowSetReader + RowReader
+ *       (src/graph/InterimResult.cpp:74-250, src/dataman/RowReader.cpp:213-258, RowSetReader.cpp)
  *   nbg_get_neighbors          ≙ StorageServiceHandler::future_getBound → QueryBoundProcessor
  *       (src/storage/StorageServiceHandler.cpp:33-40, src/storage/QueryBoundProcessor.cpp:16-220)
  */
@@ -174,6 +177,16 @@ extern "C" {
  *   constant (a non-empty derived table);
  *   an input of 2^32 rows or more; a schema and dictionary under which one row could encode to
  *   4 GiB or more (a row's length is a 32-bit word between the passes).
+ * nbg_rows_decode (tests/test_gpu_rows_decode.py holds one test per limit a test can reach; the row
+ * count and the 4 GiB chunk are guards no test reaches):
+ *   a partitioned engine (num_gpus > 1): its rows would live on several ranks;
+ *   a FLOAT field: the aligned result has no FLOAT column (InterimResult::getRows fails on it too);
+ *   more than NBG_MAX_YIELDS fields;
+ *   an input of 2^32 rows or more; a chunk of 2,048 rows whose bytes reach 4 GiB (a row's start is
+ *   a 32-bit offset from its chunk's);
+ *   a STRING cell whose bytes are not in the snapshot's dictionary (the empty string is always
+ *   there): the host route gives such strings a table of their own, which the device does not
+ *   build yet.
  * (A storage filter with a function call is E_INVALID_FILTER per part, as checkExp answers it,
  * QueryBaseProcessor.inl:172-290.)
  * Not limits: $- / $var input strings absent from the snapshot's dictionary, string functions
@@ -1030,6 +1043,64 @@ void     nbg_rowset_free(nbg_rowset* rs);
  * STRING; the rule of nbg_set_op's checkSchema above); -1 out of range. */
 int32_t  nbg_rows_col_type(const nbg_rows* r, int32_t col);
 
+/* ---- Device-resident rows from RowSetWriter bytes (the inverse of nbg_rows_encode) ----------
+ * The way back in.  When a stage answers NBG_E_UNSUPPORTED the reference's own executor produces
+ * an InterimResult on the host, and so does every `$var` a CPU executor assigned: a schema plus
+ * RowSetWriter bytes.  nbg_rows_decode makes an ordinary device-resident nbg_rows of them, the
+ * device form of what InterimResult::getRows / buildIndex do with a RowReader per row
+ * (InterimResult.cpp:74-140, 158-250; RowReader.cpp:213-258; RowSetReader.cpp), so the clauses
+ * after the fallback run on the device again.
+ * The caller keeps `data`; the result does not depend on it after the call.  The call runs under
+ * the engine lock on the engine's stream; the pinned block and the device copy of the bytes are
+ * released before it returns.
+ * The result: a device-resident nbg_rows in a workspace of its own — one segment in the input's
+ * row order, one OVER position, no string constants outside the dictionary, no derived strings,
+ * neither misaligned nor FLOAT, no step statistics, nbg_rows_edges_scanned = 0.  Every nbg_rows_*
+ * accessor works on it and every stage above takes it, nbg_go_piped and nbg_rows_encode included.
+ * nbg_rows_col_type reports col_types; nbg_rows_col_kind follows the type: INT / VID / TIMESTAMP
+ * NBG_V_INT, DOUBLE NBG_V_DOUBLE, BOOL NBG_V_BOOL, STRING NBG_V_STRING.
+ * The bytes (the read side of what nbg_rows_encode documents): row after row, varint(len(row))
+ * and the row.  The row's header byte holds offsetBytes - 1 in its low 3 bits and the count of
+ * schema-version bytes in its top 3; the version bytes are skipped, then num_cols >> 4 block
+ * offsets of offsetBytes each (the cord is walked in order, so they are not needed), then the
+ * cord's cells are read by type:
+ *   INT / TIMESTAMP  a varint of at most 10 bytes, read as uint64_t, stored as int64_t;
+ *   VID, DOUBLE      8 bytes, little endian;
+ *   BOOL             one byte, stored as 0 / 1 (a byte other than 0 / 1 is unspecified);
+ *   STRING           varint(length) and the bytes; the stored cell is the dictionary code of those
+ *                    bytes (2 x the index in the sorted dictionary), and the empty string takes the
+ *                    code every other route gives it whether or not the dictionary holds it.
+ * Bytes of the cord left over after the last cell are ignored, as RowReader ignores them.
+ * Statuses, in this order:
+ *  1. NBG_E_INVALID_ARGUMENT: a null argument; num_cols < 1; a col_types entry outside
+ *     NBG_T_BOOL..NBG_T_TIMESTAMP; len > 0 with null data.  (Then NBG_E_STATE before nbg_finalize.)
+ *  2. NBG_E_UNSUPPORTED: a partitioned engine.
+ *  3. len == 0: NBG_OK, a result of no rows with num_cols columns of those types and kinds.
+ *  4. Device scope: see "Device limits" (NBG_E_UNSUPPORTED; the caller keeps the host route): a
+ *     FLOAT field, more than NBG_MAX_YIELDS fields, 2^32 rows or more, a chunk of 2,048 rows whose
+ *     bytes reach 4 GiB.
+ *  5. NBG_E_INVALID_ARGUMENT, malformed bytes the host walk finds before any launch: a length
+ *     prefix over 10 bytes or running past len; a row running past len; a row of length 0 (it has
+ *     no header byte); a row shorter than its own header.  The message names the row and the byte.
+ *  6. NBG_E_INVALID_ARGUMENT, found on the device: a cell that would read past its row's end (a
+ *     varint cell over 10 bytes included).  The message counts such rows and names the first row
+ *     and column.
+ *  7. NBG_E_UNSUPPORTED: a STRING cell whose bytes are not in the snapshot's dictionary;
+ *     nbg_last_error says how many.
+ *  8. NBG_E_OUT_OF_MEMORY: a device or pinned allocation failed.
+ * Row starts are found by a host walk of the length-prefix chain (it is sequential, and it is the
+ * validating path); the bytes, one 8-byte start per chunk of 2,048 rows and a 32-bit offset per
+ * row go up in one DMA from a pinned block, and one launch reads the cells, a lane per row
+ * (DESIGN.md "RowSet decoding into device rows").  No input can make the kernel read outside the
+ * uploaded bytes: every read is bounded by the row's end, and the row's end by len. */
+typedef struct {
+  const uint8_t* data;        /* RowSetWriter::data(): varint(len(row)) + row, row after row */
+  uint64_t len;
+  const int32_t* col_types;   /* NBG_T_* per schema field, in field order */
+  int32_t num_cols;
+} nbg_rowset_view;
+int32_t nbg_rows_decode(nbg_engine* e, const nbg_rowset_view* rs, nbg_rows** out);
+
 /* ---- FIND SHORTEST | ALL PATH (FindPathExecutor semantics) ----------------------------- */
 typedef struct {
   const int64_t* from;           /* de-duplicated by the callee (VerticesClause::prepare)    */
@@ -1187,6 +1258,11 @@ typedef struct {
  * "GO over device rows"); the hops after them are counted under nbg_go's kernels. */
 /* ... and nbg_rows_encode's: k_re_size, k_re_scan, k_re_emit (DESIGN.md "RowSet encoding of device
  * rows"); k_re_emit's algorithmic bytes are the cells and row lengths read plus the bytes written. */
+/* ... and nbg_rows_decode's: k_rd_cells (DESIGN.md "RowSet decoding into device rows"); its algorithmic
+ * bytes are the row bytes and offsets read plus 8 x the cells written.  Two entries in front of it,
+ * rd_host_walk and rd_host_upload, are host-clock times of the call's host parts: the walk of the
+ * length prefixes, and the copy into the pinned block plus the DMA (which the call waits for only
+ * while the profile is on). */
 /* ---- FIND PATH replica of a partitioned engine (replica.hip) ---------------------------------
  * A partitioned engine (num_gpus > 1) also builds, at nbg_finalize (collectively), a replica of
  * every rank's path CSRs (offsets, neighbour ids and vids, ranks; no property columns) when it fits

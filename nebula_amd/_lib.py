@@ -118,6 +118,10 @@ class nbg_fetch_edges_request(C.Structure):
                 ("distinct", i32)]
 
 
+class nbg_rowset_view(C.Structure):
+    _fields_ = [("data", P(u8)), ("len", u64), ("col_types", P(i32)), ("num_cols", i32)]
+
+
 SET_UNION, SET_INTERSECT, SET_MINUS = 1, 2, 3
 SET_BY_NAME = {"UNION": SET_UNION, "INTERSECT": SET_INTERSECT, "MINUS": SET_MINUS}
 
@@ -176,6 +180,7 @@ SIGNATURES = [
     ("nbg_rowset_num_cols", i32, [vp]),
     ("nbg_rowset_col_type", i32, [vp, i32]),
     ("nbg_rowset_free", None, [vp]),
+    ("nbg_rows_decode", i32, [vp, P(nbg_rowset_view), P(vp)]),
     ("nbg_find_path", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_submit", i32, [vp, P(nbg_path_request), P(vp)]),
     ("nbg_find_path_wait", i32, [vp, P(vp)]),

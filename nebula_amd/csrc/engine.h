@@ -76,6 +76,7 @@ struct Engine {
   StageProf<FE_KINDS> fe_prof;                       // nbg_fetch_edges' kernels
   StageProf<GP_KINDS> gp_prof;                       // nbg_go_piped's kernels
   StageProf<RE_KINDS> re_prof;                       // nbg_rows_encode's kernels
+  StageProf<RD_KINDS> rd_prof;                       // nbg_rows_decode's host parts and kernel
   // pinned host blocks of fetched GO rows (nbg_rows_fetch), reused across queries
   std::mutex pinned_mu;
   std::vector<std::pair<size_t, void*>> pinned_free;
@@ -182,6 +183,7 @@ void for_stage_profs(Eng& E, F f) {
   f(kYaKernelNames, E.ya_prof);   // nbg_yield_agg's (yieldagg.hip)
   f(kGpKernelNames, E.gp_prof);   // nbg_go_piped's (gopipe.hip)
   f(kReKernelNames, E.re_prof);   // nbg_rows_encode's (rowenc.hip)
+  f(kRdKernelNames, E.rd_prof);   // nbg_rows_decode's (rowdec.hip)
 }
 
 int32_t engine_ready(Engine& E);   // workspace (+ partition buffers) after finalize / snapshot load

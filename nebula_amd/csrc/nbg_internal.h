@@ -1147,6 +1147,34 @@ int32_t ws_rows_encode(Workspace* inw, hipStream_t stream, const std::vector<std
                        const RePlan& plan, void* (*grow)(void* ctx, uint64_t bytes), void* ctx, uint64_t* len,
                        StageProf<RE_KINDS>* prof, std::string* err);
 
+// ---- device rows from RowSetWriter bytes (rowdec.hip, the inverse of the above; RowSetReader.cpp,
+// RowReader.cpp:213-258, InterimResult.cpp:74-140).  The host walk of rowdec.h finds every row's
+// start; one kernel reads the cells, a lane per row (DESIGN.md "RowSet decoding into device rows").
+struct RdPlan {
+  int ncols = 0;
+  uint8_t type[MAX_YIELDS] = {};   // NBG_T_* per column: how a cell is read
+  DevStrings str;                  // the dictionary (off / bytes / n): a STRING cell becomes its code
+};
+// What the kernel reports: the cells that would read past their row's end (the first as
+// row * 64 + column, ~0 when none) and the STRING cells whose bytes the dictionary lacks.
+struct RdRecord {
+  unsigned long long malformed = 0, first = ~0ull, missing = 0;
+};
+// nbg_profile_read's entries (kRdKernelNames) while nbg_profile mode 1 is on: the first two are
+// host-clock times of the call's host parts (the walk in nbg_rows_decode; the copy into the pinned
+// block plus the DMA, which the driver then waits for), the third the kernel's event time.
+enum RdKernel { RD_K_WALK = 0, RD_K_UPLOAD, RD_K_CELLS, RD_KINDS };
+extern const char* const kRdKernelNames[RD_KINDS];
+// Decodes `rows` rows of data[0, len) into a fresh rows-only workspace on `stream` (*outw;
+// ws_destroy releases it).  `block` is pinned host memory of at least rd_block_bytes(...) bytes that
+// the driver fills (the bytes, the chunk starts, the row offsets) and uploads in one DMA.
+// Synchronous; every scratch allocation is released before it returns.  NBG_OK (*rec says whether
+// the rows are good), NBG_E_OUT_OF_MEMORY or NBG_E_DEVICE (*err names the failing call).
+uint64_t rd_block_bytes(uint64_t len, uint64_t nchunks, uint64_t rows);
+int32_t ws_rows_decode(hipStream_t stream, const uint8_t* data, uint64_t len, const uint64_t* chunk_start, uint64_t nchunks,
+                       const uint32_t* row_off, uint64_t rows, void* block, const RdPlan& plan, Workspace** outw,
+                       RdRecord* rec, StageProf<RD_KINDS>* prof, std::string* err);
+
 // Query pipeline (all asynchronous on the workspace stream until ws_end_query):
 hipError_t ws_begin_query(Workspace* w, const uint32_t* starts, uint64_t n, const std::vector<TypeProgram>* progs,
                           uint64_t stmt_id);

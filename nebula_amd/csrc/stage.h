@@ -1,5 +1,5 @@
 // nebula_amd — the frame of a driver of a stage over device-resident rows (groupby.hip, orderby.hip,
-// setops.hip, yieldrows.hip, yieldagg.hip, fetchrows.hip, fetchedges.hip, gopipe.hip, rowenc.hip): the status of its HIP calls, its result workspace
+// setops.hip, yieldrows.hip, yieldagg.hip, fetchrows.hip, fetchedges.hip, gopipe.hip, rowenc.hip, rowdec.hip): the status of its HIP calls, its result workspace
 // (RowsWs, nbg_internal.h), the scratch of one call, the event pairs nbg_profile puts around each
 // launch, the chunk list that spreads an input's segments over the device, and the YrPlan setup
 // YIELD and FETCH share.  A driver declares its scratch before its timer: the timer's events are

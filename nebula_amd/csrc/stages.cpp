@@ -1,15 +1,17 @@
 // The stages over device-resident rows at the C ABI (include/nbg.h): nbg_group_by, nbg_order_by,
-// nbg_set_op, nbg_yield, nbg_yield_agg, nbg_fetch_vertices, nbg_fetch_edges and nbg_rows_encode.  Each
-// plans its request on the host, as its executor in the reference checks it, and hands the plan to its
-// driver (groupby.hip, orderby.hip, setops.hip, yieldrows.hip, yieldagg.hip, fetchrows.hip,
-// fetchedges.hip, rowenc.hip).
+// nbg_set_op, nbg_yield, nbg_yield_agg, nbg_fetch_vertices, nbg_fetch_edges, nbg_rows_encode and
+// nbg_rows_decode.  Each plans its request on the host, as its executor in the reference checks it, and
+// hands the plan to its driver (groupby.hip, orderby.hip, setops.hip, yieldrows.hip, yieldagg.hip,
+// fetchrows.hip, fetchedges.hip, rowenc.hip, rowdec.hip).
 #include <algorithm>
+#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
 #include <set>
 
 #include "nbg_rows.h"
+#include "rowdec.h"
 #include "rowenc.h"
 
 using namespace nbg;
@@ -1641,6 +1643,92 @@ void nbg_rowset_free(nbg_rowset* rs) {
   if (!rs) return;
   if (rs->eng && rs->data) rs->eng->pinned_put(rs->data, rs->cap);
   delete rs;
+}
+
+// ============================================================================= RowSet decoding
+// The way back in: what InterimResult::getRows / buildIndex read with a RowReader per row
+// (InterimResult.cpp:74-140, 158-250; RowReader.cpp:213-258; RowSetReader.cpp) becomes an ordinary
+// device-resident result.  The walk and the cell reader are in rowdec.h, the kernel in rowdec.hip.
+int32_t nbg_rows_decode(nbg_engine* h, const nbg_rowset_view* rs, nbg_rows** out) {
+  if (!h || !rs || !out) return NBG_E_INVALID_ARGUMENT;
+  *out = nullptr;
+  Engine& E = h->e;
+  std::lock_guard<std::mutex> lg(E.mu);
+  // ---- 1. arguments
+  if (!rs->col_types) return E.fail(NBG_E_INVALID_ARGUMENT, "rows decode: null argument");
+  if (rs->num_cols < 1) return E.fail(NBG_E_INVALID_ARGUMENT, "rows decode: a schema without fields");
+  const int nc = rs->num_cols;
+  for (int c = 0; c < nc; ++c)
+    if (rs->col_types[c] < NBG_T_BOOL || rs->col_types[c] > NBG_T_TIMESTAMP)
+      return E.fail(NBG_E_INVALID_ARGUMENT, "rows decode: field " + std::to_string(c) + " has no NBG_T_* type");
+  if (rs->len && !rs->data) return E.fail(NBG_E_INVALID_ARGUMENT, "rows decode: null data");
+  if (!E.finalized) return E.fail(NBG_E_STATE, "engine not finalized");
+  // ---- 2.
+  if (int32_t rc = guard_partitioned(E, "rows decode")) return rc;
+  std::unique_ptr<nbg_rows> res(new_rows(E, nc));
+  for (int c = 0; c < nc; ++c) {
+    res->col_types[c] = rs->col_types[c];
+    res->kinds[0][c] = kindOfType(rs->col_types[c]);
+  }
+  // ---- 3.
+  if (!rs->len) {
+    *out = res.release();
+    return NBG_OK;
+  }
+  // ---- 4. device scope: the schema, then what only the walk can tell
+  if (nc > MAX_YIELDS) return E.fail(NBG_E_UNSUPPORTED, "rows decode: more than NBG_MAX_YIELDS fields");
+  RdPlan plan;
+  plan.ncols = nc;
+  for (int c = 0; c < nc; ++c) {
+    if (rs->col_types[c] == NBG_T_FLOAT)
+      return E.fail(NBG_E_UNSUPPORTED, "rows decode: a FLOAT field (the aligned result has no FLOAT column)");
+    plan.type[c] = (uint8_t)rs->col_types[c];
+  }
+  const auto t0 = std::chrono::steady_clock::now();
+  const RdIndex ix = rd_walk(rs->data, rs->len, nc);
+  if (E.rd_prof.on) {
+    E.rd_prof.launches[RD_K_WALK]++;
+    E.rd_prof.ms[RD_K_WALK] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    E.rd_prof.bytes[RD_K_WALK] += (double)rs->len;
+  }
+  if (ix.status == RD_WALK_ROWS) return E.fail(NBG_E_UNSUPPORTED, "rows decode: an input of 2^32 rows or more");
+  if (ix.status == RD_WALK_CHUNK)
+    return E.fail(NBG_E_UNSUPPORTED, "rows decode: a chunk of 2,048 rows whose bytes reach 4 GiB");
+  // ---- 5. malformed bytes
+  if (rd_walk_malformed(ix.status)) {
+    const char* what = ix.status == RD_WALK_PREFIX     ? "a length prefix over 10 bytes or running past the end"
+                       : ix.status == RD_WALK_PAST_END ? "a row running past the end"
+                       : ix.status == RD_WALK_EMPTY_ROW ? "a row of length 0 (no header byte)"
+                                                        : "a row shorter than its own header";
+    return E.fail(NBG_E_INVALID_ARGUMENT, std::string("rows decode: ") + what + " (row " + std::to_string(ix.bad_row) +
+                                              ", byte " + std::to_string(ix.bad_at) + ")");
+  }
+  // ---- the pass
+  if (hipSetDevice(E.cfg.device) != hipSuccess) return E.fail(NBG_E_DEVICE, "hipSetDevice failed");
+  plan.str = E.dev_strings();
+  size_t cap = 0;
+  void* block = E.pinned_get((size_t)rd_block_bytes(rs->len, ix.chunk_start.size(), ix.rows), &cap);
+  if (!block) return E.fail(NBG_E_OUT_OF_MEMORY, "rows decode: pinned host memory for the row bytes");
+  Workspace* ow = nullptr;
+  RdRecord rec;
+  std::string err;
+  const int32_t rc = ws_rows_decode(E.stream, rs->data, rs->len, ix.chunk_start.data(), ix.chunk_start.size(), ix.row_off.data(),
+                                    ix.rows, block, plan, &ow, &rec, &E.rd_prof, &err);
+  E.pinned_put(block, cap);
+  if (rc) return E.fail(rc, err);
+  RowsWs hold;   // (destroyed unless the result adopts it)
+  hold.w = ow;
+  // ---- 6., 7.
+  if (rec.malformed)
+    return E.fail(NBG_E_INVALID_ARGUMENT, "rows decode: " + std::to_string(rec.malformed) +
+                                              " row(s) whose cells would read past the row's end; the first is row " +
+                                              std::to_string(rec.first >> 6) + ", column " + std::to_string(rec.first & 63));
+  if (rec.missing)
+    return E.fail(NBG_E_UNSUPPORTED, "rows decode: " + std::to_string(rec.missing) +
+                                         " STRING cell(s) whose bytes are not in the snapshot's dictionary");
+  adopt_rows(res.get(), hold.release(), ix.rows, nc);
+  *out = res.release();
+  return NBG_OK;
 }
 
 }  // extern "C"

@@ -572,6 +572,17 @@ class Engine:
         self._check(self.lib.nbg_fetch_edges(self.h, handle, C.byref(req), C.byref(out)), "fetch_edges")
         return DeviceRows(self, out)
 
+    def rows_decode(self, data: bytes, types) -> DeviceRows:
+        """nbg_rows_decode: the RowSetWriter bytes of an InterimResult (``data``) under the schema's
+        NBG_T_* field types become a device-resident result that every stage accepts — the inverse of
+        ``DeviceRows.encode``.  ``data`` is not referenced after the call."""
+        buf = np.frombuffer(bytes(data), np.uint8)
+        t = (C.c_int32 * max(1, len(types)))(*[int(x) for x in types])
+        view = L.nbg_rowset_view(buf.ctypes.data_as(C.POINTER(C.c_uint8)) if len(buf) else None, len(buf), t, len(types))
+        out = C.c_void_p()
+        self._check(self.lib.nbg_rows_decode(self.h, C.byref(view), C.byref(out)), "rows decode")
+        return DeviceRows(self, out)
+
     def default_columns(self, etypes, over_all=False):
         """Edge types of a YIELD-less GO's `<edge>._dst` columns, in column order (OVER order;
         for OVER *, the response edge_schema's iteration order, GoExecutor.cpp:481-499)."""
